@@ -32,15 +32,24 @@ every step into its own generation of slots; all slots are zeroed after the
 warmup and every slot a timed step wrote is checked on the device afterwards
 (verify_mismatches / verify_coverage).
 
-Every untimed section after the timed steps is bounded by one deadline counted
+A plain run ends there: set-up, posting selection, warmup, the timed steps,
+their verification, the JSON line.  --dump-outputs DIR also writes what the
+last timed step delivered to each rank (DIR/recv_rank<r>.npy, float32 byte
+values; a fixed, seeded sample of every message where the step moved more than
+the files may hold), identical from run to run with the same arguments.
+
+--full adds the untimed sections after the timed steps: p50 latency, the
+reference's methodology and ours on its serial schedule, the other BASELINE
+configs (all-pairs, ring, ring hop, the size sweep), the same steps through
+the IPC engines, the xGMI pair sweep.  They are bounded by one deadline counted
 from process start (--deadline): each section's waits are shortened to the
 time left, sections that would not fit are skipped (untimed_skipped), and a
 watchdog prints the JSON line with what is done when the deadline passes.
 
-At N = 2 on two distinct GPUs the time the deadline leaves after every other
-section goes to the xGMI pair-cell tuning sweep (scripts/xgmi_pair_sweep.py:
-RCCL communicator counts, the IPC engines, RCCL knobs; every row verified),
-recorded in xgmi_pair_sweep.
+With --full at N = 2 on two distinct GPUs the time the deadline leaves after
+every other section goes to the xGMI pair-cell tuning sweep
+(scripts/xgmi_pair_sweep.py: RCCL communicator counts, the IPC engines, RCCL
+knobs; every row verified), recorded in xgmi_pair_sweep.
 
 Should RCCL itself fail on every rank (a communicator that cannot be set up, a
 connection or transfer that stalls past --timeout), the same steps are timed
@@ -49,7 +58,7 @@ null and the IPC number is kept beside it (headline_fallback.value_gbs);
 --fallback 0 reports the error alone.
 
 Usage (driver contract):
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -178,6 +187,15 @@ def parse_args(argv=None):
                     help="receive-slot memory per rank (0: 40%% of free HBM / ranks per GPU); caps the slot "
                          "generations, and so verify_coverage")
     ap.add_argument("--json-out", default=None, help="also write the result line to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed sections (latency, the reference's methodology, "
+                         "the other BASELINE configs, the IPC comparisons, the xGMI pair sweep); without it the run "
+                         "ends with the headline and those fields of the line stay null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step delivered to each rank as "
+                         "DIR/recv_rank<r>.npy (float32 byte values; a fixed sample of 4 KiB chunks of every message "
+                         "when the step's deliveries exceed the size limit) and DIR/recv_rank<r>_chunks.npy (float64 "
+                         "rows: message, sender, byte offset, length)")
     ap.add_argument("--ipc-extra", type=int, default=1,
                     help="1: also run the timed steps through the IPC engines (pull, push, sdma; relay from N = 3) "
                          "after the timed region, untimed by the contract, each in a child process per rank")
@@ -337,6 +355,15 @@ class BenchRun(HeadlineMixin, SectionsMixin):
         self.log0("bench: value %.2f GB/s per cell (aggregate %.2f GB/s), %.4f ms/step, verify %s" % (
             h.value, h.aggregate, h.elapsed / self.args.steps * 1e3, h.vr))
 
+        if self.args.full:
+            self.untimed_sections()
+        else:
+            h.sess = h.ref_sess = h.sessions = None
+        return self.report()
+
+    def untimed_sections(self):
+        """--full: everything measured after the timed steps."""
+        h = self.h
         self.untimed_t0 = time.monotonic()
         self.timeline.begin("untimed")
         self.plan_sections()
@@ -351,6 +378,9 @@ class BenchRun(HeadlineMixin, SectionsMixin):
         self.comparisons()
         self.xgmi_sweep_section()
 
+    def report(self) -> int:
+        """The JSON line, then the teardown; returns the exit status."""
+        h = self.h
         self.timeline.begin("report")
         self.reporter.update(untimed_skipped=self.state["skipped"] or None,
                              section_errors=self.state["errors"] or None)

@@ -472,6 +472,14 @@ PYBIND11_MODULE(_p2pcore, m) {
            "Host time each recorded step took to post (ms).")
       .def("reset", [](PyStepDriver& s) { s.d().reset(); })
       .def("verify_last", [](PyStepDriver& s) { return s.d().verify_last(); }, py::call_guard<NativeCall, py::gil_scoped_release>())
+      .def("deliveries", [](PyStepDriver& s, long k) {
+            std::vector<std::tuple<uintptr_t, size_t, int, int>> out;
+            for (const auto& x : s.d().deliveries(k))
+              out.emplace_back(reinterpret_cast<uintptr_t>(x.p), s.d().msg_bytes(), x.src, x.msg);
+            return out;
+          }, py::arg("step"),
+           "This rank's receive slots of step `step`, in message order: [(address, bytes, sender, message)] "
+           "(read them after sync()).")
       .def("bytes_sent_per_step", [](PyStepDriver& s, long k) { return s.d().bytes_sent_per_step(k); })
       .def("job_bytes_per_step", [](PyStepDriver& s, long k) { return s.d().job_bytes_per_step(k); })
       .def_property_readonly("phases", [](PyStepDriver& s) { return s.d().phases(); })

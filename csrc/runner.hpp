@@ -316,6 +316,15 @@ class StepDriver {
   // count) against the payload of the message that wrote it last.
   StepVerifyReport verify_steps(long first, long count);
   uint64_t verify_last();       // mismatches in the receive slots of the last step (collective)
+  // What step k delivered to THIS rank: one entry per message and sender, in
+  // message order (local, read-only; the slot holds `bytes` after sync()).
+  struct Delivery {
+    const void* p = nullptr;
+    int src = -1;
+    int msg = 0;
+  };
+  std::vector<Delivery> deliveries(long k) const;
+  size_t msg_bytes() const { return bytes_; }
   double bytes_sent_per_step(long k) const;  // by THIS rank
   double job_bytes_per_step(long k) const;   // by all ranks
   int flows_per_step(long k) const;          // directed flows of step k's phase

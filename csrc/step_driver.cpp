@@ -329,6 +329,19 @@ uint64_t StepDriver::verify_last() {
   return verify_steps(last_step_, 1).mismatches;
 }
 
+std::vector<StepDriver::Delivery> StepDriver::deliveries(long k) const {
+  P2P_CHECK(k >= 0, "bad step");
+  const int me = t_.rank();
+  const int pi = static_cast<int>(k % phases());
+  const RankOps& ops = sched_.phases[static_cast<size_t>(pi)].ranks[static_cast<size_t>(me)];
+  std::vector<Delivery> out;
+  out.reserve(static_cast<size_t>(msgs_) * ops.recv_from.size());
+  for (int m = 0; m < msgs_; ++m)
+    for (size_t i = 0; i < ops.recv_from.size(); ++i)
+      out.push_back({bufs_.recv_buf(slot_index(me, gen_of(k), pi, m, static_cast<int>(i))), ops.recv_from[i], m});
+  return out;
+}
+
 double StepDriver::bytes_sent_per_step(long k) const {
   const Phase& p = sched_.phases[static_cast<size_t>(k % static_cast<long>(sched_.phases.size()))];
   return static_cast<double>(p.ranks[static_cast<size_t>(t_.rank())].send_to.size()) * static_cast<double>(bytes_) * msgs_;

@@ -14,6 +14,6 @@ timeout -k 10 150 /opt/conda/bin/mpirun -n $N ./build/p2p_matrix --device 0 --mo
 timeout -k 10 150 /opt/conda/bin/mpirun -n $N ./build/p2p_matrix --device 0 --comms 4 --mode tournament,ring,allpairs \
   --size 4M -n 4 --verify --no-compat --timeout 60 > gpurun_out/rccl_emu/cli_n${N}_k4.txt 2>&1 &&
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-  --master-port $((29870 + N)) bench.py --gpus $N --device 0 --size 4M --msgs 8 --sweep-max 64M --allpairs-size 64M \
+  --master-port $((29870 + N)) bench.py --full --gpus $N --device 0 --size 4M --msgs 8 --sweep-max 64M --allpairs-size 64M \
   --ring-size 16M --ref-iters 16 --latency-iters 50 --ipc-extra 0 --timeout 60 --deadline 380 \
   --json-out gpurun_out/rccl_emu/bench_n$N.json > /dev/null 2> gpurun_out/rccl_emu/bench_n$N.err

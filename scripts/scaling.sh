@@ -15,10 +15,10 @@ for N in 1 2 4 8; do
   if [ "$N" -gt "$NGPU" ]; then break; fi
   PORT=$((29500 + RANDOM % 2000))
   if [ "$N" -eq 1 ]; then
-    timeout -k 10 600 python3 bench.py --gpus 1 "$@" >> "$OUT"
+    timeout -k 10 600 python3 bench.py --full --gpus 1 "$@" >> "$OUT"
   else
     timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
-      --master-addr 127.0.0.1 --master-port "$PORT" bench.py --gpus "$N" "$@" >> "$OUT"
+      --master-addr 127.0.0.1 --master-port "$PORT" bench.py --full --gpus "$N" "$@" >> "$OUT"
   fi
 done
 python3 - "$OUT" <<'PY'

@@ -21,6 +21,14 @@ from test_nccl_p2p_amd.bench.faults import emulate_hang
 from test_nccl_p2p_amd.utils.report import FALLBACK, SELF_COPY, XGMI_LINK
 
 
+# --dump-outputs: the .npy files of all ranks together hold at most DUMP_BYTES
+# (float32, four bytes per payload byte), sampled in chunks of DUMP_CHUNK
+# payload bytes drawn from DUMP_SEED.
+DUMP_BYTES = 48 << 20
+DUMP_CHUNK = 4096
+DUMP_SEED = 20260
+
+
 def hw_queues() -> int:
     """GPU_MAX_HW_QUEUES in effect for this process (HIP's default: 4)."""
     try:
@@ -166,6 +174,10 @@ class HeadlineMixin:
         if vr is not None:
             vr["seconds"] = round(time.perf_counter() - v0, 4)
         depth, recv_bytes = drv.depth, drv.recv_bytes
+        dumped = None
+        if args.dump_outputs:
+            tl.begin(pre + "headline/dump_outputs")
+            dumped = self.dump_outputs(drv, args.warmup + args.steps - 1)
         # Everything after this is untimed; release the timed driver's buffers
         # first so the comparisons run on the same memory footprint as the
         # timed steps did.
@@ -177,7 +189,62 @@ class HeadlineMixin:
             aggregate=aggregate, my_ms=my_ms, matrix=matrix, samples=samples, cells=cells, offdiag=offdiag,
             expected=n * (n - 1) if n > 1 else 1, vr=vr, mismatches=vr["mismatches"] if vr else -1, depth=depth,
             recv_bytes=recv_bytes, chunking=chunking, rccl_peers=rccl_peers, matrix_transport=matrix_transport,
-            host_post_ms=(t_posted - t0) * 1e3, post_ms=post_ms)
+            host_post_ms=(t_posted - t0) * 1e3, post_ms=post_ms, dumped=dumped)
+
+    def dump_outputs(self, drv, step: int) -> dict:
+        """--dump-outputs DIR: what timed step `step` (the last one) delivered
+        to this rank -- the receive slots a caller of the step reads, one per
+        message and sender -- as DIR/recv_rank<r>.npy, float32 byte values.  All
+        ranks together stay under DUMP_BYTES: where the step's deliveries are
+        larger, every message contributes its first and last 4 KiB chunk and a
+        sample of the ones between, drawn from a fixed seed per message, so two
+        runs with the same arguments write the same bytes of the same messages
+        (the payloads are PRNG streams seeded by sender, size and message).
+        DIR/recv_rank<r>_chunks.npy lists the chunks, one float64 row each:
+        message, sender, byte offset in the message, length.  Local to the
+        rank; the steps are synced by now."""
+        import ctypes
+        import random
+
+        import numpy as np
+
+        slots = drv.deliveries(step)
+        rows, chunk = [], DUMP_CHUNK
+        if slots:
+            per_slot = max(1, DUMP_BYTES // 4 // self.n // len(slots) // chunk)
+            for ptr, nbytes, src, msg in slots:
+                nchunks = max(1, -(-nbytes // chunk))
+                if nchunks <= per_slot:
+                    picks = range(nchunks)
+                else:
+                    ends = [0, nchunks - 1][:per_slot]
+                    rng = random.Random(DUMP_SEED + msg * 1009 + src)
+                    picks = sorted(ends + rng.sample(range(1, nchunks - 1), min(per_slot - len(ends), nchunks - 2)))
+                rows += [(msg, src, c * chunk, min(chunk, nbytes - c * chunk), ptr + c * chunk) for c in picks]
+        rows = rows[:max(1, DUMP_BYTES // 4 // self.n // chunk)]  # (more messages than chunks fit: the first ones)
+        total = sum(r[3] for r in rows)
+        if self.use_gpu:
+            # The gfx950 copy kernel gathers the chunks into one staging
+            # tensor, a whole chunk apart (16-byte aligned, as it requires).
+            stage = torch.zeros(max(len(rows), 1) * chunk, dtype=torch.uint8, device="cuda:%d" % self.device)
+            torch.cuda.synchronize()
+            base = stage.data_ptr()
+            ops = [(base + i * chunk, r[4], r[3]) for i, r in enumerate(rows)]
+            for i in range(0, len(ops), 1024):
+                self.nat.copy_many(ops[i:i + 1024])
+            torch.cuda.synchronize()
+            host = stage.cpu().numpy().reshape(-1, chunk)
+            data = np.concatenate([host[i, :r[3]] for i, r in enumerate(rows)]) if rows else np.zeros(0, np.uint8)
+        else:
+            data = np.frombuffer(b"".join(ctypes.string_at(r[4], r[3]) for r in rows), dtype=np.uint8)
+        os.makedirs(self.args.dump_outputs, exist_ok=True)
+        name = "recv_rank%d" % self.env.rank
+        np.save(os.path.join(self.args.dump_outputs, name + ".npy"), data.astype(np.float32))
+        np.save(os.path.join(self.args.dump_outputs, name + "_chunks.npy"),
+                np.array([r[:4] for r in rows], dtype=np.float64).reshape(-1, 4))
+        return {"dir": self.args.dump_outputs, "step": step, "file": name + ".npy", "messages": len(slots),
+                "chunks": len(rows), "bytes_sampled": total,
+                "bytes_delivered": sum(s[1] for s in slots)}
 
     def select_posting(self, transport, choices, c0, sessions, session_for, first_budget, phases, pre):
         """Posting selection: whole untimed laps of the schedule per candidate
@@ -520,6 +587,10 @@ class HeadlineMixin:
             "ipc_transport": None,
             "xgmi_pair_sweep": None,
             "untimed_skipped": None,
+            # False: the run ended with the headline (no --full), the untimed
+            # sections' fields above are null because they were not asked for.
+            "full": bool(args.full),
+            "outputs_dumped": h.dumped,
             "headline_fallback": fallback,
             "note": ("n_gpus=1 has no inter-GPU link: value is RCCL's on-GPU self send/recv copy (HBM-bound), the "
                      "diagonal the reference prints as 0.00. From n_gpus=2 every step is one tournament round of "

@@ -70,7 +70,7 @@ def test_repeat_self_summary(exe, tmp_path):
 
 
 def test_bench_contract_single_gpu():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--latency-iters", "50"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--latency-iters", "50"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -166,7 +166,7 @@ def test_bench_drops_a_failing_communicator_candidate():
     eight with bench.py's 8 hardware queues) instead; with one warmup step it
     falls back the same way."""
     for warmup in ("1", "4"):
-        out = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", warmup, "--latency-iters", "20",
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", warmup, "--latency-iters", "20",
                               "--ref-stock", "0"],
                              capture_output=True, text=True, timeout=600, cwd=ROOT,
                              env=dict(os.environ, P2P_BENCH_FAIL_CANDIDATE="4,1"))
@@ -186,7 +186,7 @@ def test_bench_chunks_around_rccl_half_delivery():
     (P2P_RCCL_MAX_CHUNK=0) the bench's verified warmup sees the loss, caps the
     ops at 16 MiB, and the timed steps verify; with the fallback off too
     (P2P_RECHUNK=0) the loss reaches the timed check: exit 3."""
-    base = [sys.executable, "bench.py", "--steps", "4", "--warmup", "2", "--comms", "1", "--ipc-extra", "0",
+    base = [sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "2", "--comms", "1", "--ipc-extra", "0",
             "--ref-iters", "0", "--latency-iters", "20"]
     runs = {}
     for name, extra, rc in (("transport", {}, 0), ("fallback", {"P2P_RCCL_MAX_CHUNK": "0"}, 0),
@@ -216,7 +216,7 @@ def test_bench_headline_falls_back_to_ipc():
     """Should RCCL fail on the node (injected on every rank), the timed steps
     run through the IPC data plane and the line names the fallback; the
     metric is RCCL's, so value is null and the IPC number sits beside it."""
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "2", "--latency-iters", "20",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "2", "--latency-iters", "20",
                           "--ref-iters", "8", "--ipc-extra", "0"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT,
                          env=dict(os.environ, P2P_BENCH_FAIL_HEADLINE="rccl"))
@@ -249,7 +249,7 @@ def test_bench_real_rccl_failure_falls_back():
     on both ranks; the timed steps run through the IPC data plane instead,
     verified, and the line names the RCCL error."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "3",
+           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "2", "--steps", "6", "--warmup", "3",
            "--size", "4M", "--msgs", "4", "--sweep", "0", "--extras", "0", "--ref-iters", "0", "--latency-iters", "20",
            "--ipc-extra", "0", "--timeout", "60"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)

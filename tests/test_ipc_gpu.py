@@ -184,7 +184,7 @@ def test_bench_two_ranks_ipc_push():
     the time left (--xgmi-sweep 1: ranks sharing the GPU, so its IPC rows run
     emulated, each an mpirun job of build/p2p_matrix, verified)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "3",
+           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "2", "--steps", "6", "--warmup", "3",
            "--transport", "ipc:push", "--device", "0", "--latency-iters", "50", "--sweep-max", "64M", "--ipc-extra", "0",
            "--xgmi-sweep", "1", "--xgmi-sweep-sizes", "4M"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -201,7 +201,7 @@ def test_bench_two_ranks_ipc_push():
 
 def test_bench_two_ranks_ipc():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "3",
+           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "2", "--steps", "6", "--warmup", "3",
            "--transport", "ipc", "--device", "0", "--latency-iters", "50"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -224,7 +224,7 @@ def test_bench_emulated_node(nranks):
     sweep, the reference-method matrix and the pull / push comparisons all
     run through the N-rank code paths the 8-GPU scaling run uses."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks),
-           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", str(nranks),
+           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", str(nranks),
            "--steps", "14", "--warmup", "7", "--transport", "ipc", "--device", "0", "--sweep-max", "64M",
            "--latency-iters", "100", "--deadline", "560",
            # N ranks share one GPU's memory: 32 messages per step keep every

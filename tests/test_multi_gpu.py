@@ -144,7 +144,7 @@ def test_concurrent_modes_all_gpus(exe):
 def test_bench_all_gpus():
     n = _n()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", str(n), "--steps", "14",
+           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", str(n), "--steps", "14",
            "--warmup", "7", "--deadline", "80", "--sweep-max", "256M", "--timeout", "45"] + BENCH_MSGS + ISOLATE
     out = run_logged(cmd, BUDGET_S["test_bench_all_gpus"], "bench_all_gpus", cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -209,7 +209,7 @@ def test_bench_two_gpus_pair_sweep():
     are off here (test_bench_all_gpus runs them), so the sweep has the time:
     the one-GPU rehearsal with them on skipped it for lack of time."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--steps", "14", "--warmup", "7",
+           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "2", "--steps", "14", "--warmup", "7",
            "--deadline", "75", "--xgmi-sweep-sizes", "32M", "--ipc-extra", "0", "--extras", "0", "--sweep", "0",
            "--ref-iters", "0", "--latency-preposted", "0", "--latency-iters", "50",
            "--timeout", "45"] + BENCH_MSGS + (["--xgmi-sweep", "1"] if REHEARSAL else [])

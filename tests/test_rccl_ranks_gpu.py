@@ -70,7 +70,7 @@ def test_bench_four_rccl_ranks(tmp_path):
     tournament steps with every delivery verified, and every untimed section."""
     out_json = tmp_path / "b.json"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "4", "--device", "0", "--size", "4M",
+           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "4", "--device", "0", "--size", "4M",
            "--msgs", "8", "--sweep-max", "16M", "--allpairs-size", "16M", "--ring-size", "8M", "--ref-iters", "8",
            "--latency-iters", "30", "--ipc-extra", "0", "--timeout", "60", "--json-out", str(out_json)]
     out = run_logged(cmd, 400, "bench_four_rccl_ranks", cwd=ROOT, env=ENV)
@@ -126,7 +126,7 @@ def test_bench_deadline_aborts_rccl_inside_and_outside_the_engine(tmp_path):
     request and aborts them on the main thread).  Both end with exit 4
     (nothing measured) and neither crashes."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--device", "0", "--size", "4M",
+           "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--full", "--gpus", "2", "--device", "0", "--size", "4M",
            "--msgs", "4", "--ipc-extra", "0", "--timeout", "60", "--deadline", "25"]
     env = dict(ENV, P2P_BENCH_HANG="candidate:rccl:1,0:stall@1;candidate:rccl:1,0:unbounded@0")
     out = run_logged(cmd, 90, "bench_deadline_abort", cwd=ROOT, env=env)

@@ -39,7 +39,7 @@ def test_native_module_under_torchrun(native):
 
 
 def test_bench_cpu_two_ranks(native):
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--transport", "host",
                        "--size", "256K", "--msgs", "2", "--latency-iters", "20", "--sweep-max", "1M"])
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -75,7 +75,7 @@ def test_bench_runs_the_pair_sweep_in_the_time_left(native, host_build):
     scripts/xgmi_pair_sweep.py (here on the CPU host transport) in the time
     the deadline leaves and the line carries its verified rows and winner;
     without the option a CPU run skips it (auto: N = 2 on distinct GPUs)."""
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--transport", "host",
                        "--size", "64K", "--msgs", "1", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ipc-extra", "0", "--xgmi-sweep", "1", "--xgmi-sweep-sizes", "64K"])
     assert out.returncode == 0, out.stderr[-3000:]
@@ -85,7 +85,7 @@ def test_bench_runs_the_pair_sweep_in_the_time_left(native, host_build):
     assert sw["rows"]["host"]["rc"] == 0 and sw["rows"]["host"]["uni/65536"]["cell_gbs"] > 0, sw
     assert sw["best"]["bi/65536"]["row"] == "host" and sw["budget_s"] > 0
     # A sweep that cannot run is an error in its field, not a failed bench.
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--transport", "host",
                        "--size", "64K", "--msgs", "1", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ipc-extra", "0", "--xgmi-sweep", "1"], env={"P2P_MPIRUN": "/nonexistent/mpirun"})
     assert out.returncode == 0, out.stderr[-3000:]
@@ -101,7 +101,7 @@ def test_bench_pair_sweep_row_that_hangs_is_killed(native, host_build, tmp_path)
     fake = tmp_path / "hanging_mpirun.sh"
     fake.write_text("#!/bin/sh\nsleep 600\n")
     fake.chmod(0o755)
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--transport", "host",
                        "--size", "64K", "--msgs", "1", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ipc-extra", "0", "--xgmi-sweep", "1", "--xgmi-sweep-sizes", "64K", "--deadline", "120"],
                    env={"P2P_MPIRUN": str(fake), "P2P_XGMI_SWEEP_ROW_TIMEOUT": "10"})
@@ -117,7 +117,7 @@ def test_bench_pair_sweep_row_that_hangs_is_killed(native, host_build, tmp_path)
 def test_bench_comparison_failure_is_isolated(native):
     """A comparison process that dies or hangs (here: killed at its time
     limit) is reported in the JSON; the headline line is still printed."""
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "2", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "2", "--transport", "host",
                        "--size", "64K", "--msgs", "1", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ref-iters", "0", "--child-timeout", "0.05"])
     assert out.returncode == 0, out.stderr[-3000:]
@@ -134,7 +134,7 @@ def test_session_api_under_torchrun(native):
 def test_bench_drops_a_failing_posting_candidate(native):
     """A warmup candidate that fails on one rank is dropped on every rank and
     reported; the run goes on with the others."""
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "4", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "4", "--transport", "host",
                        "--size", "64K", "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ref-iters", "0", "--ipc-extra", "0"], env={"P2P_BENCH_FAIL_CANDIDATE": "1,1"})
     assert out.returncode == 0, out.stderr[-3000:]
@@ -145,7 +145,7 @@ def test_bench_drops_a_failing_posting_candidate(native):
 
 def test_bench_drops_a_candidate_failing_in_warmup(native):
     """The same when the candidate connects but its tuning lap fails."""
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "4", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "4", "--transport", "host",
                        "--size", "64K", "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ref-iters", "0", "--ipc-extra", "0"], env={"P2P_BENCH_FAIL_CANDIDATE": "1,1,tuning"})
     assert out.returncode == 0, out.stderr[-3000:]
@@ -154,7 +154,7 @@ def test_bench_drops_a_candidate_failing_in_warmup(native):
     assert r["posting"]["dropped"]["comms1_batch"] in ("injected tuning failure", "failed on another rank")
 
 
-HANG_ARGS = ["bench.py", "--gpus", "4", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "64K",
+HANG_ARGS = ["bench.py", "--full", "--gpus", "4", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "64K",
              "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0", "--ref-iters", "0",
              "--ipc-extra", "0", "--deadline", "120", "--fallback-to", "shm"]
 
@@ -212,7 +212,7 @@ def test_bench_deadline_aborts_inside_and_outside_the_engine(native):
     transport for rank 1's messages (its wait sees the request and aborts on
     the main thread).  Both exit 4: nothing was measured."""
     t0 = time.monotonic()
-    args = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "64K",
+    args = ["bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "64K",
             "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0", "--ref-iters", "0",
             "--ipc-extra", "0", "--deadline", "30"]
     out = torchrun(2, args,
@@ -237,7 +237,7 @@ def test_bench_teardown_after_the_line_never_fails_the_run(native):
     before the others': its process started earlier) breaks their final
     barrier; the line is out by then, so every rank still exits 0 (the
     8-rank rehearsal exited 1, profiles/r5_reh8b/)."""
-    args = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "64K",
+    args = ["bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "64K",
             "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0", "--ref-iters", "0",
             "--ipc-extra", "0", "--deadline", "25"]
     out = torchrun(2, args, env={"P2P_BENCH_HANG": "teardown@1"}, timeout=120)
@@ -259,7 +259,7 @@ def test_fuzz_session_over_shm_and_host(native):
 def test_bench_untimed_budget_skips_sections(native):
     """With the untimed budget spent, every section after the timed steps is
     skipped on all ranks together and listed; the headline line still comes."""
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "2", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "2", "--transport", "host",
                        "--size", "64K", "--msgs", "1", "--latency-iters", "10", "--untimed-budget", "0"])
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -273,7 +273,7 @@ def test_bench_value_is_the_mean_cell(native):
     """value is the mean per-flow, per-direction rate from the wall clock; it
     agrees with the matrix built from per-step GPU (here host) timelines, and
     aggregate_gbs is the sum over the flows of a step."""
-    out = torchrun(4, ["bench.py", "--gpus", "4", "--steps", "9", "--warmup", "3", "--transport", "shm",
+    out = torchrun(4, ["bench.py", "--full", "--gpus", "4", "--steps", "9", "--warmup", "3", "--transport", "shm",
                        "--size", "4M", "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ref-iters", "0", "--ipc-extra", "0", "--batch", "1"])
     assert out.returncode == 0, out.stderr[-3000:]
@@ -289,7 +289,7 @@ def test_bench_skipped_transfers_fail_verification(native):
     """P2P_INJECT_FAULT=skip@1: rank 1's transport silently moves no payload in
     the timed steps.  The warmup had delivered everything, so only poisoning
     after the warmup plus one slot per timed message can catch it: exit 3."""
-    out = torchrun(2, ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host",
+    out = torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host",
                        "--size", "64K", "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ref-iters", "0", "--ipc-extra", "0"], env={"P2P_INJECT_FAULT": "skip@1"})
     assert out.returncode != 0
@@ -306,7 +306,7 @@ def test_bench_deadline_with_a_hung_section(native, hung):
     import time as _time
 
     t0 = _time.monotonic()
-    out = torchrun(4, ["bench.py", "--gpus", "4", "--steps", "3", "--warmup", "2", "--transport", "host",
+    out = torchrun(4, ["bench.py", "--full", "--gpus", "4", "--steps", "3", "--warmup", "2", "--transport", "host",
                        "--size", "64K", "--msgs", "1", "--latency-iters", "10", "--sweep", "0", "--ipc-extra", "0",
                        "--deadline", "80"], env={"P2P_BENCH_HANG": "latency@%d" % hung}, timeout=200)
     wall = _time.monotonic() - t0
@@ -343,7 +343,7 @@ def test_bench_eight_ranks_with_the_driver_step_counts(native):
     # (2 MiB x 8 messages: a tuning pass takes ~75-110 ms here, long enough
     # for the timeline check below; at 256 KiB x 4 a 10 ms pass drowned in
     # the scheduling noise of 8 processes on 8 CPUs.)
-    out = torchrun(8, ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5", "--transport", "shm",
+    out = torchrun(8, ["bench.py", "--full", "--gpus", "8", "--steps", "20", "--warmup", "5", "--transport", "shm",
                        "--size", "2M", "--msgs", "8", "--recv-budget", "512M", "--sweep-max", "4M", "--ref-iters", "8",
                        "--latency-iters", "50", "--allpairs-size", "16M", "--ring-size", "4M"], timeout=300)
     wall = time.monotonic() - t0
@@ -400,7 +400,7 @@ def test_bench_headline_fallback(native):
     steps, but the line does not pass that off as the metric: value is null
     and the fallback's number sits in headline_fallback.value_gbs.  With
     --fallback 0 the line carries the error and value null."""
-    args = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "256K",
+    args = ["bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--transport", "host", "--size", "256K",
             "--msgs", "2", "--latency-iters", "20", "--sweep", "0", "--extras", "0", "--ref-iters", "0",
             "--ipc-extra", "0", "--fallback-to", "shm"]
     out = torchrun(2, args, env={"P2P_BENCH_FAIL_HEADLINE": "host"})
@@ -427,7 +427,7 @@ def _xgmi_speed_rehearsal(deadline):
     of ~50 GB/s per direction.  The pair sweep stops at 256 KiB (256 MiB on the
     node): its iteration count follows absolute sizes."""
     t0 = time.monotonic()
-    out = torchrun(8, ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5", "--transport", "shm",
+    out = torchrun(8, ["bench.py", "--full", "--gpus", "8", "--steps", "20", "--warmup", "5", "--transport", "shm",
                        "--size", "32K", "--allpairs-size", "1M", "--ring-size", "256K", "--sweep-max", "256K",
                        "--ipc-extra", "0", "--deadline", str(deadline)], timeout=deadline + 60,
                    env={"P2P_EMULATE_LINK_GBS": "0.0488"})
@@ -472,7 +472,7 @@ def test_bench_four_ranks_repeat_the_reference_matrices(native):
     runs more than once in its slice; the line keeps each run's mean cell and
     their median / min / max, and the method ratio is the ratio of the
     medians."""
-    out = torchrun(4, ["bench.py", "--gpus", "4", "--steps", "3", "--warmup", "2", "--transport", "host",
+    out = torchrun(4, ["bench.py", "--full", "--gpus", "4", "--steps", "3", "--warmup", "2", "--transport", "host",
                        "--size", "64K", "--msgs", "2", "--latency-iters", "10", "--sweep", "0", "--extras", "0",
                        "--ref-iters", "8", "--ipc-extra", "0"])
     assert out.returncode == 0, out.stderr[-3000:]
@@ -496,7 +496,7 @@ def test_bench_one_rank_self_sweep(native):
     in powers of 4 up to --sweep-max, every size verified; here over the CPU
     host transport.  The reference-method matrices repeat --ref-runs times
     (each run is milliseconds at N = 1)."""
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "1", "--steps", "3", "--warmup", "2",
                           "--transport", "host", "--size", "64K", "--msgs", "2", "--latency-iters", "10",
                           "--sweep-max", "1M", "--ref-iters", "8", "--ipc-extra", "0"],
                          capture_output=True, text=True, timeout=240, cwd=ROOT,
