@@ -452,7 +452,9 @@ LaunchGeom fill_geometry(size_t bytes, FillImpl) {
   return g;
 }
 
-LaunchGeom verify_geometry(size_t bytes, VerifyImpl impl, unsigned max_grid) {
+LaunchGeom verify_geometry(size_t bytes, VerifyImpl impl, unsigned max_grid, int lds_stages) {
+  P2P_CHECK(lds_stages == 0 || lds_stages == 4 || lds_stages == kLdsStages,
+            "verify: lds_stages must be 0 (by size), 4 or 8");
   LaunchGeom g;
   const uint64_t nvec = bytes / 16;
   if (impl == VerifyImpl::Auto) impl = kDefaultVerify;
@@ -468,11 +470,12 @@ LaunchGeom verify_geometry(size_t bytes, VerifyImpl impl, unsigned max_grid) {
     g.grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min(tiles, cap)));
   } else {
     // Waves of 4 or 8 KiB chunks (lds_stages_for), and the LDS each wave owns.
-    const int stages = lds_stages_for(bytes);
+    const int stages = lds_stages ? lds_stages : lds_stages_for(bytes);
     const uint64_t sc_vecs = static_cast<uint64_t>(stages) * 64;
     const uint64_t waves = (nvec + sc_vecs - 1) / sc_vecs;
     g.grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min((waves + kWaves - 1) / kWaves, cap)));
     g.lds_bytes = sizeof(uint4) * kWaves * stages * 64;
+    g.lds_stages = stages;
   }
   return g;
 }
@@ -508,7 +511,7 @@ void launch_verify_t(const uint4* vp, uint64_t nvec, uint64_t seed, const uint8_
                      VerifyImpl impl, const LaunchGeom& g, hipStream_t stream) {
   if (impl == VerifyImpl::Stride)
     verify_stride_kernel<CHECK><<<g.grid, kBlock, 0, stream>>>(vp, nvec, seed, tp, tail, nvec * 16, acc);
-  else if (lds_stages_for(nvec * 16) == 4)
+  else if (g.lds_stages == 4)
     verify_lds_kernel<CHECK, 4><<<g.grid, kBlock, 0, stream>>>(vp, nvec, seed, tp, tail, nvec * 16, acc);
   else
     verify_lds_kernel<CHECK, kLdsStages><<<g.grid, kBlock, 0, stream>>>(vp, nvec, seed, tp, tail, nvec * 16, acc);
@@ -516,7 +519,9 @@ void launch_verify_t(const uint4* vp, uint64_t nvec, uint64_t seed, const uint8_
 }  // namespace
 
 void launch_verify(const void* p, size_t bytes, uint64_t seed, VerifyAccum* acc, VerifyImpl impl, bool check_prng,
-                   hipStream_t stream, unsigned max_grid) {
+                   hipStream_t stream, unsigned max_grid, int lds_stages) {
+  P2P_CHECK(lds_stages == 0 || lds_stages == 4 || lds_stages == kLdsStages,
+            "verify: lds_stages must be 0 (by size), 4 or 8");
   if (bytes) {
     P2P_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, "verify: buffer must be 16-byte aligned");
     if (impl == VerifyImpl::Auto) impl = kDefaultVerify;
@@ -524,7 +529,7 @@ void launch_verify(const void* p, size_t bytes, uint64_t seed, VerifyAccum* acc,
     const uint32_t tail = static_cast<uint32_t>(bytes - nvec * 16);
     const auto* vp = static_cast<const uint4*>(p);
     const auto* tp = static_cast<const uint8_t*>(p) + nvec * 16;
-    LaunchGeom g = verify_geometry(bytes, impl, max_grid);
+    LaunchGeom g = verify_geometry(bytes, impl, max_grid, lds_stages);
     if (check_prng)
       launch_verify_t<true>(vp, nvec, seed, tp, tail, acc, impl, g, stream);
     else

@@ -62,19 +62,26 @@ struct LaunchGeom {
   unsigned grid = 0;
   unsigned block = 256;
   size_t lds_bytes = 0;
+  int lds_stages = 0;  // LDS-staged verify: KiB each wave stages per pass (4 or 8); 0 for the stride kernel
 };
 
 LaunchGeom fill_geometry(size_t bytes, FillImpl impl = FillImpl::Auto);
 // max_grid > 0 caps the workgroup count (the kernels grid-stride beyond it);
-// 0 = the tuned default of the variant.
-LaunchGeom verify_geometry(size_t bytes, VerifyImpl impl, unsigned max_grid = 0);
+// 0 = the tuned default of the variant.  lds_stages picks the LDS-staged
+// kernel's template: 0 = by size (4 KiB per wave below 2 GiB, 8 KiB from
+// there), 4 or 8 force that one at any size (tests reach either kernel's
+// loop on small buffers); anything else fails a P2P_CHECK.  The stride
+// kernel ignores the value.  The returned geometry is what launch_verify
+// launches: grid, LDS bytes and template.
+LaunchGeom verify_geometry(size_t bytes, VerifyImpl impl, unsigned max_grid = 0, int lds_stages = 0);
 
 void launch_fill(void* p, size_t bytes, uint64_t seed, hipStream_t stream, FillImpl impl = FillImpl::Auto);
 void launch_verify_reset(VerifyAccum* acc, hipStream_t stream);
 // check_prng=false only sums the words (checksum of an arbitrary buffer).
-// Leaves the totals in acc[0] (stream-ordered).
+// Leaves the totals in acc[0] (stream-ordered).  max_grid and lds_stages as
+// in verify_geometry (0, 0: the production launch).
 void launch_verify(const void* p, size_t bytes, uint64_t seed, VerifyAccum* acc, VerifyImpl impl, bool check_prng,
-                   hipStream_t stream, unsigned max_grid = 0);
+                   hipStream_t stream, unsigned max_grid = 0, int lds_stages = 0);
 
 // ---- batched verify (the post-timing check of many receive slots) ----
 // Job i's totals land in out[i] (device memory, njobs entries; nothing needs

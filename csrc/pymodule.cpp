@@ -279,14 +279,24 @@ dev::VerifyImpl verify_impl_arg(int impl) {
   return static_cast<dev::VerifyImpl>(impl);
 }
 
-py::tuple device_verify(uintptr_t ptr, size_t bytes, uint64_t seed, int impl, bool check, uintptr_t stream) {
+// 0 (the kernel by size), 4 or 8 (that template at any size); checked before
+// any device work.
+int lds_stages_arg(int lds_stages) {
+  if (lds_stages != 0 && lds_stages != 4 && lds_stages != 8)
+    throw py::value_error(strfmt("verify: lds_stages %d is not 0 (by size), 4 or 8", lds_stages));
+  return lds_stages;
+}
+
+py::tuple device_verify(uintptr_t ptr, size_t bytes, uint64_t seed, int impl, bool check, uintptr_t stream,
+                        unsigned max_grid, int lds_stages) {
   const dev::VerifyImpl vi = verify_impl_arg(impl);
+  lds_stages_arg(lds_stages);
   KernelScratch& ks = scratch();
   hipStream_t st = as_stream(stream);
   {
     py::gil_scoped_release nogil;
     dev::launch_verify_reset(ks.d, st);
-    dev::launch_verify(reinterpret_cast<const void*>(ptr), bytes, seed, ks.d, vi, check, st);
+    dev::launch_verify(reinterpret_cast<const void*>(ptr), bytes, seed, ks.d, vi, check, st, max_grid, lds_stages);
     if (hipMemcpyAsync(ks.h, ks.d, sizeof(dev::VerifyAccum), hipMemcpyDeviceToHost, st) != hipSuccess)
       P2P_FATAL("hipMemcpyAsync failed");
     if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
@@ -501,23 +511,26 @@ PYBIND11_MODULE(_p2pcore, m) {
       }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("stream") = 0, py::arg("impl") = 0,
       "impl: 0 auto = 1 full grid (one 16 B store per lane, one 4 KiB block per workgroup)");
   m.def("verify", &device_verify, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("impl") = 0,
-        py::arg("check") = true, py::arg("stream") = 0,
-        "impl: 0 auto (= 1), 1 LDS-DMA staged (lds8), 2 register staged (stride).  Returns (mismatching words, "
+        py::arg("check") = true, py::arg("stream") = 0, py::arg("max_grid") = 0, py::arg("lds_stages") = 0,
+        "impl: 0 auto (= 1), 1 LDS-DMA staged (lds8), 2 register staged (stride).  max_grid > 0 caps the workgroup "
+        "count; lds_stages 4 or 8 forces that LDS-staged kernel (0: by size).  Returns (mismatching words, "
         "checksum, first bad byte offset or 2**64-1).");
   m.def("verify_many", &device_verify_many, py::arg("jobs"), py::arg("stream") = 0,
         "Batched verify of [(ptr, bytes, seed)]: one (mismatches, checksum, first_bad) per job, one readback.");
   m.def("verify_many_launch", &device_verify_many_launch, py::arg("jobs"), py::arg("stream") = 0,
         "Stream-ordered batched verify launches only (timing).");
   m.def("verify_launch", [](uintptr_t ptr, size_t bytes, uint64_t seed, int impl, bool check, uintptr_t stream,
-                            unsigned max_grid) {
+                            unsigned max_grid, int lds_stages) {
         // Stream-ordered launch only (reset + verify + finalize), no readback:
         // for timing the kernel with events.
         const dev::VerifyImpl vi = verify_impl_arg(impl);
+        lds_stages_arg(lds_stages);
         KernelScratch& ks = scratch();
         dev::launch_verify_reset(ks.d, as_stream(stream));
-        dev::launch_verify(reinterpret_cast<const void*>(ptr), bytes, seed, ks.d, vi, check, as_stream(stream), max_grid);
+        dev::launch_verify(reinterpret_cast<const void*>(ptr), bytes, seed, ks.d, vi, check, as_stream(stream), max_grid,
+                           lds_stages);
       }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("impl") = 0, py::arg("check") = true,
-      py::arg("stream") = 0, py::arg("max_grid") = 0);
+      py::arg("stream") = 0, py::arg("max_grid") = 0, py::arg("lds_stages") = 0);
   m.def("copy", [](uintptr_t dst, uintptr_t src, size_t bytes, uintptr_t stream, int max_blocks, bool coherent) {
         dev::CopyOp op{reinterpret_cast<const void*>(src), reinterpret_cast<void*>(dst), bytes, coherent};
         dev::launch_multi_copy(&op, 1, as_stream(stream), max_blocks);
@@ -526,22 +539,23 @@ PYBIND11_MODULE(_p2pcore, m) {
       "The IPC transport's gfx950 copy kernel on one (dst, src) pair (coherent: the cross-GPU form with "
       "system-scope sc0 sc1 buffer loads and stores).");
   m.def("copy_many", [](const std::vector<std::tuple<uintptr_t, uintptr_t, size_t>>& ops, uintptr_t stream,
-                        bool coherent) {
+                        bool coherent, int max_blocks) {
         std::vector<dev::CopyOp> v;
         for (const auto& o : ops)
           v.push_back({reinterpret_cast<const void*>(std::get<1>(o)), reinterpret_cast<void*>(std::get<0>(o)),
                        std::get<2>(o), coherent});
-        dev::launch_multi_copy(v.data(), static_cast<int>(v.size()), as_stream(stream));
-      }, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false,
-      "The copy kernel over several (dst, src, bytes) ops, as the IPC transport launches a group's receives.");
+        dev::launch_multi_copy(v.data(), static_cast<int>(v.size()), as_stream(stream), max_blocks);
+      }, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0,
+      "The copy kernel over several (dst, src, bytes) ops, as the IPC transport launches a group's receives "
+      "(max_blocks > 0: the ops of a launch share that many workgroups and grid-stride).");
   m.def("fill_geometry", [](size_t bytes) {
     auto g = dev::fill_geometry(bytes);
     return py::make_tuple(g.grid, g.block, g.lds_bytes);
   });
-  m.def("verify_geometry", [](size_t bytes, int impl) {
-    auto g = dev::verify_geometry(bytes, verify_impl_arg(impl));
+  m.def("verify_geometry", [](size_t bytes, int impl, unsigned max_grid, int lds_stages) {
+    auto g = dev::verify_geometry(bytes, verify_impl_arg(impl), max_grid, lds_stages_arg(lds_stages));
     return py::make_tuple(g.grid, g.block, g.lds_bytes);
-  });
+  }, py::arg("bytes"), py::arg("impl"), py::arg("max_grid") = 0, py::arg("lds_stages") = 0);
   m.def("rccl_available", &rccl_transport_available);
   m.def("runtime_json", &runtime_json, "HIP runtime / RCCL library versions and paths, visible devices and links.");
   m.def("env_knobs_json", &env_knobs_json, "Every NCCL_/RCCL_/HSA_/HIP_/GPU_... environment knob that is set.");

@@ -60,17 +60,24 @@ def fill_(t: torch.Tensor, seed: int, stream: Optional[torch.cuda.Stream] = None
     return t
 
 
-def verify(t: torch.Tensor, seed: int, impl: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> VerifyResult:
-    """Compares ``t`` with PRNG stream ``seed`` on the device (blocking)."""
+def verify(t: torch.Tensor, seed: int, impl: str = "auto", stream: Optional[torch.cuda.Stream] = None, *,
+           max_grid: int = 0, lds_stages: int = 0) -> VerifyResult:
+    """Compares ``t`` with PRNG stream ``seed`` on the device (blocking).
+    ``max_grid`` > 0 caps the workgroup count and ``lds_stages`` 4 or 8 forces
+    that LDS-staged kernel (0, 0: the production launch)."""
     nbytes = _check_tensor(t)
-    r = require_native().verify(t.data_ptr(), nbytes, seed & (2**64 - 1), impl_number(impl), True, _stream(stream))
+    r = require_native().verify(t.data_ptr(), nbytes, seed & (2**64 - 1), impl_number(impl), True, _stream(stream),
+                                max_grid=max_grid, lds_stages=lds_stages)
     return VerifyResult(*r)
 
 
-def checksum(t: torch.Tensor, impl: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> int:
-    """Sum of the tensor's 32-bit words mod 2**64 (no PRNG compare)."""
+def checksum(t: torch.Tensor, impl: str = "auto", stream: Optional[torch.cuda.Stream] = None, *,
+             max_grid: int = 0, lds_stages: int = 0) -> int:
+    """Sum of the tensor's 32-bit words mod 2**64 (no PRNG compare);
+    ``max_grid`` and ``lds_stages`` as in :func:`verify`."""
     nbytes = _check_tensor(t)
-    return int(require_native().verify(t.data_ptr(), nbytes, 0, impl_number(impl), False, _stream(stream))[1])
+    return int(require_native().verify(t.data_ptr(), nbytes, 0, impl_number(impl), False, _stream(stream),
+                                       max_grid=max_grid, lds_stages=lds_stages)[1])
 
 
 # ---------------------------------------------------------------- reference --
