@@ -25,8 +25,8 @@ OPT       ?= -O3
 HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
-CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate) kernels.o pingpong.o)
+CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate) kernels.o diagnose_hip.o pingpong.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in
@@ -97,6 +97,10 @@ $(BUILD)/gpu/%.o: csrc/%.cpp $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/gpu/kernels.o: csrc/kernels.hip $(HEADERS) | $(BUILD)/gpu
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# csrc/diagnose.cpp (host side, in CORE) owns diagnose.o.
+$(BUILD)/gpu/diagnose_hip.o: csrc/diagnose.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/gpu/pingpong.o: csrc/pingpong.hip $(HEADERS) | $(BUILD)/gpu

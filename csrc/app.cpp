@@ -100,6 +100,10 @@ data
       --no-verify        zero-filled sends, nothing read back (the reference's data)
       --verify-impl I    auto (= lds8) | lds8 (alias lds) | stride (alias reg)
                          (LDS-DMA- or register-staged verify kernel)
+      --diagnose N       after a failed check, each rank says where its first N wrong
+                         (generation, slot) deliveries differ and what they hold instead:
+                         poison, a stale generation, another sender's or a misplaced
+                         payload, or flipped bits (stderr lines, "diagnosis" in --json)  [0]
 transport / launch
       --transport T      rccl  MI355X + RCCL ncclSend/ncclRecv over xGMI      [rccl]
                          ipc   one-sided pulls from hipIpc-mapped peer buffers (gfx950 copy
@@ -150,7 +154,8 @@ environment (recorded in every --json provenance record; docs/OUTPUT.md)
   P2P_BOOTSTRAP_PORT, P2P_BOOTSTRAP_TIMEOUT   TCP bootstrap port / receive deadline
   P2P_HOSTNAME=name      hostname for the placement check (emulated hosts)
   P2P_DEVICE=N           default of --device
-  P2P_INJECT_FAULT=kind@rank[:phase]   corrupt | exit | hang | skip | skip-some (tests)
+  P2P_DIAGNOSE=N         default of --diagnose
+  P2P_INJECT_FAULT=kind@rank[:phase]   corrupt | exit | hang | skip | skip-some | stale (tests)
   P2P_ROCTX=1, P2P_LOG=1 roctx ranges; engine log on stderr
 )";
 }
@@ -184,6 +189,8 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
   // P2P_DEVICE: the default of --device (a multi-GPU rehearsal on one GPU
   // puts every rank on device 0 without editing the command lines).
   if (const char* d = std::getenv("P2P_DEVICE"); d && *d) cfg->device = std::atoi(d);
+  // P2P_DIAGNOSE: the default of --diagnose.
+  if (const char* d = std::getenv("P2P_DIAGNOSE"); d && *d) cfg->run.diagnose = std::max(0, std::atoi(d));
   for (int i = 0; i < argc; ++i) {
     std::string a = argv[i];
     std::string val;
@@ -239,7 +246,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     static const char* kValued[] = {"-m", "--mode", "-d", "--dir", "-b", "--size", "--sizes", "-n", "--iters", "-w",
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
-                                    "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat"};
+                                    "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -318,6 +325,8 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       cfg->run.verify = true;
     } else if (a == "--no-verify") {
       cfg->run.verify = false;
+    } else if (a == "--diagnose") {
+      cfg->run.diagnose = int_arg(0);
     } else if (a == "--verify-impl") {
       const std::string v = next();
       std::string note;

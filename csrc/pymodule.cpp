@@ -103,7 +103,8 @@ class Session {
 
   // One (mode, dir, size) run; returns the run JSON (report.cpp schema).
   std::string run(const std::string& mode, const std::string& dir, size_t bytes, int iters, int warmup,
-                  const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells) {
+                  const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
+                  int diagnose) {
     Schedule s = make_schedule(parse_mode(mode), parse_direction(dir), world());
     restrict_cells(&s, cells, true);
     RunConfig cfg;
@@ -113,6 +114,7 @@ class Session {
     cfg.timing = parse_timing(timing);
     cfg.verify = verify;
     cfg.salt = ++salt_;
+    cfg.diagnose = std::max(0, diagnose);
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
@@ -358,6 +360,110 @@ void device_verify_many_launch(const std::vector<std::tuple<uintptr_t, size_t, u
   dev::launch_multi_verify(dj.data(), n, b.scratch, b.out, as_stream(stream));
 }
 
+// ---- mismatch diagnosis (diagnose.hpp) ----
+// Candidates cross as (seed, shift[, kind[, value]]) tuples; granule records
+// as (index, first_bad, last_bad, zero, other, flipped_bits, cand0..cand5),
+// damaged granules only; extents as (begin, end, zero, other, flipped_bits,
+// cand0..cand5).
+std::vector<DiagCandidate> candidates_arg(const std::vector<py::tuple>& in) {
+  if (in.size() > static_cast<size_t>(kMaxDiagCandidates))
+    throw py::value_error(strfmt("diagnose: at most %d candidates", kMaxDiagCandidates));
+  std::vector<DiagCandidate> out;
+  for (const py::tuple& t : in) {
+    if (t.size() < 2 || t.size() > 4) throw py::value_error("diagnose: a candidate is (seed, shift[, kind[, value]])");
+    DiagCandidate c;
+    c.seed = t[0].cast<uint64_t>();
+    c.shift = t[1].cast<int64_t>();
+    if (t.size() > 2) c.kind = t[2].cast<int>();
+    if (t.size() > 3) c.value = t[3].cast<int64_t>();
+    if (c.shift % 16) throw py::value_error("diagnose: a candidate's shift must be a multiple of 16 bytes");
+    out.push_back(c);
+  }
+  return out;
+}
+
+size_t granule_arg(size_t granule, size_t bytes) {
+  if (!granule) return diagnose_granule(bytes);
+  if (granule < kMinDiagGranule || (granule & (granule - 1)))
+    throw py::value_error("diagnose: the granule must be a power of two, at least 4 KiB");
+  return granule;
+}
+
+py::list records_py(const DiagRecord* recs, size_t n) {
+  py::list out;
+  for (size_t i = 0; i < n; ++i) {
+    const DiagRecord& r = recs[i];
+    if (!r.damaged()) continue;
+    out.append(py::make_tuple(i, r.first_bad(), r.last_bad(), r.zero, r.other, r.flipped_bits, r.cand[0], r.cand[1],
+                              r.cand[2], r.cand[3], r.cand[4], r.cand[5]));
+  }
+  return out;
+}
+
+py::tuple extent_py(const DiagExtent& e) {
+  return py::make_tuple(e.begin, e.end, e.zero, e.other, e.flipped_bits, e.cand[0], e.cand[1], e.cand[2], e.cand[3],
+                        e.cand[4], e.cand[5]);
+}
+
+// One per device, never destroyed (like KernelScratch).
+dev::Diagnoser* diagnoser() {
+  static auto* per_device = new std::vector<dev::Diagnoser*>();
+  int dv = 0;
+  if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
+  if (static_cast<int>(per_device->size()) <= dv) per_device->resize(static_cast<size_t>(dv) + 1, nullptr);
+  dev::Diagnoser*& dg = (*per_device)[static_cast<size_t>(dv)];
+  if (!dg) dg = new dev::Diagnoser();
+  return dg;
+}
+
+py::list device_diagnose(uintptr_t ptr, size_t bytes, uint64_t seed, const std::vector<py::tuple>& candidates,
+                         size_t granule, uintptr_t stream, unsigned max_grid) {
+  const std::vector<DiagCandidate> c = candidates_arg(candidates);
+  granule = granule_arg(granule, bytes);
+  dev::Diagnoser* dg = diagnoser();
+  hipStream_t st = as_stream(stream);
+  {
+    py::gil_scoped_release nogil;
+    dg->enqueue(reinterpret_cast<const void*>(ptr), bytes, seed, c.data(), static_cast<int>(c.size()), granule, st,
+                max_grid);
+    if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
+  }
+  return records_py(dg->records(), dg->count());
+}
+
+py::list merge_extents_py(const std::vector<py::tuple>& records, size_t bytes, size_t granule) {
+  granule = granule_arg(granule, bytes);
+  std::vector<DiagRecord> dense(diagnose_records(bytes, granule), DiagRecord{});
+  for (const py::tuple& t : records) {
+    if (t.size() != 6 + kMaxDiagCandidates) throw py::value_error("merge_extents: a record has 12 fields");
+    const size_t i = t[0].cast<size_t>();
+    if (i >= dense.size()) throw py::value_error("merge_extents: record index past the buffer");
+    DiagRecord& r = dense[i];
+    r.first_enc = ~t[1].cast<uint64_t>();
+    r.last_enc = t[2].cast<uint64_t>() + 1;
+    r.zero = t[3].cast<uint64_t>();
+    r.other = t[4].cast<uint64_t>();
+    r.flipped_bits = t[5].cast<uint64_t>();
+    for (int k = 0; k < kMaxDiagCandidates; ++k) r.cand[k] = t[6 + static_cast<size_t>(k)].cast<uint64_t>();
+  }
+  py::list out;
+  for (const DiagExtent& e : merge_extents(dense.data(), dense.size(), bytes, granule)) out.append(extent_py(e));
+  return out;
+}
+
+std::string describe_extent_py(const py::tuple& t, size_t bytes, const std::vector<py::tuple>& candidates) {
+  if (t.size() != 5 + kMaxDiagCandidates) throw py::value_error("describe_extent: an extent has 11 fields");
+  const std::vector<DiagCandidate> c = candidates_arg(candidates);
+  DiagExtent e;
+  e.begin = t[0].cast<uint64_t>();
+  e.end = t[1].cast<uint64_t>();
+  e.zero = t[2].cast<uint64_t>();
+  e.other = t[3].cast<uint64_t>();
+  e.flipped_bits = t[4].cast<uint64_t>();
+  for (int k = 0; k < kMaxDiagCandidates; ++k) e.cand[k] = t[5 + static_cast<size_t>(k)].cast<uint64_t>();
+  return describe_extent(e, bytes, c.data(), static_cast<int>(c.size()));
+}
+
 py::list schedule_py(const std::string& mode, const std::string& dir, int n) {
   Schedule s = make_schedule(parse_mode(mode), parse_direction(dir), n);
   py::list phases;
@@ -402,7 +508,8 @@ PYBIND11_MODULE(_p2pcore, m) {
       .def("allreduce_sum", &Session::allreduce_sum, py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("run", &Session::run, py::arg("mode") = "pair", py::arg("dir") = "uni", py::arg("bytes") = 32u << 20,
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
-           py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::call_guard<NativeCall, py::gil_scoped_release>())
+           py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
+           py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("device_latency", &Session::device_latency, py::arg("bytes") = 8, py::arg("iters") = 1000,
@@ -587,6 +694,39 @@ PYBIND11_MODULE(_p2pcore, m) {
     VerifyResult r = host_verify(s.data(), s.size(), seed);
     return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
   });
+  // ---- mismatch diagnosis ----
+  m.attr("MAX_DIAG_CANDIDATES") = kMaxDiagCandidates;
+  m.def("diagnose", &device_diagnose, py::arg("ptr"), py::arg("bytes"), py::arg("seed"),
+        py::arg("candidates") = std::vector<py::tuple>{}, py::arg("granule") = 0, py::arg("stream") = 0,
+        py::arg("max_grid") = 0,
+        "The gfx950 diagnosis kernel on a device buffer (blocking): the damaged granules, each (index, first_bad, "
+        "last_bad, zero, other, flipped_bits, cand0..cand5) with first_bad / last_bad the byte offsets of its first "
+        "and last damaged word.  candidates: up to 6 (seed, shift) with shift a multiple of 16 bytes; granule 0: "
+        "by size; max_grid > 0 caps the workgroup count.");
+  m.def("diagnose_launch", [](uintptr_t ptr, size_t bytes, uint64_t seed, const std::vector<py::tuple>& candidates,
+                              size_t granule, uintptr_t stream, unsigned max_grid) {
+        // Stream-ordered launch only (the records' memset + the kernel), no
+        // readback: for timing the kernel with events.
+        const std::vector<DiagCandidate> c = candidates_arg(candidates);
+        diagnoser()->enqueue(reinterpret_cast<const void*>(ptr), bytes, seed, c.data(), static_cast<int>(c.size()),
+                             granule_arg(granule, bytes), as_stream(stream), max_grid, false);
+      }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("candidates") = std::vector<py::tuple>{},
+      py::arg("granule") = 0, py::arg("stream") = 0, py::arg("max_grid") = 0);
+  m.def("host_diagnose", [](py::bytes data, uint64_t seed, const std::vector<py::tuple>& candidates, size_t granule) {
+        const std::string s = data;
+        const std::vector<DiagCandidate> c = candidates_arg(candidates);
+        granule = granule_arg(granule, s.size());
+        const auto recs = host_diagnose(s.data(), s.size(), seed, c.data(), static_cast<int>(c.size()), granule);
+        return records_py(recs.data(), recs.size());
+      }, py::arg("data"), py::arg("seed"), py::arg("candidates") = std::vector<py::tuple>{}, py::arg("granule") = 0,
+      "CPU implementation of diagnose, the same records bit for bit.");
+  m.def("merge_extents", &merge_extents_py, py::arg("records"), py::arg("bytes"), py::arg("granule") = 0,
+        "Damaged granules -> extents (begin, end, zero, other, flipped_bits, cand0..cand5): maximal runs of "
+        "consecutive damaged granules with the same set of non-zero classes.");
+  m.def("describe_extent", &describe_extent_py, py::arg("extent"), py::arg("bytes"),
+        py::arg("candidates") = std::vector<py::tuple>{}, "One line saying what an extent's words hold instead.");
+  m.def("diagnose_granule", &diagnose_granule, py::arg("bytes"),
+        "The default granule: the smallest power of two >= 4 KiB with at most 65536 records for the buffer.");
   m.def("prng_word", &prng_word);
   m.def("payload_seed", &payload_seed);
 

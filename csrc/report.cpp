@@ -334,7 +334,26 @@ std::string run_to_json(const RunRecord& rec, int n) {
       if (f.verified) o << ",\"mismatches\":" << f.mismatches << ",\"checksum\":" << f.checksum;
       o << "}";
     }
-    o << "]}";
+    o << "]";
+    // RunConfig::diagnose: present only when something was found.
+    if (!ph.diagnosis.empty()) {
+      o << ",\"diagnosis\":[";
+      for (size_t i = 0; i < ph.diagnosis.size(); ++i) {
+        const SlotDiagnosis& s = ph.diagnosis[i];
+        o << (i ? "," : "") << "{\"src\":" << s.src << ",\"dst\":" << s.dst << ",\"gen\":" << s.gen
+          << ",\"more_extents\":" << s.more_extents << ",\"more_words\":" << s.more_words << ",\"extents\":[";
+        for (size_t e = 0; e < s.extents.size(); ++e) {
+          const DiagExtent& x = s.extents[e];
+          o << (e ? "," : "") << "{\"begin\":" << x.begin << ",\"end\":" << x.end << ",\"zero\":" << x.zero
+            << ",\"other\":" << x.other << ",\"flipped_bits\":" << x.flipped_bits << ",\"cand\":[";
+          for (int k = 0; k < kMaxDiagCandidates; ++k) o << (k ? "," : "") << x.cand[k];
+          o << "],\"text\":\"" << json_escape(s.text[e]) << "\"}";
+        }
+        o << "]}";
+      }
+      o << "]";
+    }
+    o << "}";
     first = false;
   }
   o << "]}";

@@ -221,9 +221,10 @@ void prepare_payload(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
   if (cfg.verify) zero_slots(t, phase, cfg, bufs, gens);
 }
 
-// Wrong words in this rank's receive slots of generations [0, gens).
+// Wrong words in this rank's receive slots of generations [0, gens);
+// per_job: those of each (generation, slot), generation-major.
 uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buffers& bufs, int gens,
-                     std::vector<uint64_t>* per_slot = nullptr) {
+                     std::vector<uint64_t>* per_slot = nullptr, std::vector<uint64_t>* per_job = nullptr) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const int per = std::max(1, phase.max_recv_slots());
   std::vector<Transport::VerifyJob> jobs;
@@ -237,6 +238,7 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
     for (size_t i = 0; i < ops.recv_from.size(); ++i, ++k) {
       const VerifyResult& v = res[static_cast<size_t>(k)];
       bad += v.mismatches;
+      if (per_job) per_job->push_back(v.mismatches);
       if (per_slot) {
         (*per_slot)[2 * i] += v.mismatches;
         if (g == 0) (*per_slot)[2 * i + 1] = v.checksum;
@@ -255,6 +257,11 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
 //   skip-some — the same for every other timed iteration (the even ones):
 //             caught only because every iteration has its own receive
 //             generation (RunConfig::gens),
+//   stale   — after the timed loop, when the phase has at least two
+//             generations, receive slot 0 of generation 0 is refilled with
+//             generation 1's stream of the same sender: a whole delivery that
+//             is a valid payload, only not the one due (the diagnosis must name
+//             it, RunConfig::diagnose), exit 2,
 //   exit    — the rank dies abruptly (peers must fail, not hang),
 //   hang    — the rank stops responding (peers' watchdogs must fire).
 struct FaultSpec {
@@ -294,13 +301,20 @@ bool fault_applies(const char* kind, int rank, long phase_index) {
 
 namespace {
 
-void maybe_inject_fault(Transport& t, Buffers& bufs, int rank, size_t phase_index, size_t bytes) {
+void maybe_inject_fault(Transport& t, Buffers& bufs, int rank, size_t phase_index, size_t bytes, const Phase& phase,
+                        uint64_t salt, int gens) {
   const FaultSpec& f = fault_spec();
   if (f.kind.empty() || f.kind == "skip" || f.kind == "skip-some" || f.rank != rank) return;
   if (f.phase >= 0 && static_cast<size_t>(f.phase) != phase_index) return;
   if (f.kind == "corrupt") {
     if (bufs.slots() > 0) {
       t.zero(bufs.recv_buf(0), std::min<size_t>(bytes, 64));
+      t.sync();
+    }
+  } else if (f.kind == "stale") {
+    const RankOps& ops = phase.ranks[static_cast<size_t>(rank)];
+    if (gens >= 2 && !ops.recv_from.empty()) {
+      t.fill(bufs.recv_buf(0), bytes, generation_seed(ops.recv_from[0], bytes, salt, 1));
       t.sync();
     }
   } else if (f.kind == "exit") {
@@ -386,6 +400,123 @@ size_t phase_op_bytes(const Transport& t, const Phase& phase, size_t bytes) {
   for (int p : ops.send_to) see(p);
   for (int p : ops.recv_from) see(p);
   return split ? most : 0;
+}
+
+// ---- diagnosis of the slots the timed check found wrong (RunConfig::diagnose)
+
+// The streams a wrong word of (generation g, sender `src`) is compared with,
+// in order: the sender's neighbouring generations, its own stream one op
+// further on and one op earlier (when messages are posted as smaller ops),
+// then the same generation's payloads of the rank's other senders.
+std::vector<DiagCandidate> slot_candidates(const RankOps& ops, const RunConfig& cfg, int src, int g, int gens,
+                                           size_t op_bytes) {
+  std::vector<DiagCandidate> c;
+  auto add = [&](uint64_t seed, int64_t shift, int kind, int64_t value) {
+    if (c.size() >= static_cast<size_t>(kMaxDiagCandidates)) return;
+    DiagCandidate d;
+    d.seed = seed;
+    d.shift = shift;
+    d.kind = kind;
+    d.value = value;
+    c.push_back(d);
+  };
+  if (gens >= 2) {
+    const int prev = (g + gens - 1) % gens, next = (g + 1) % gens;
+    add(generation_seed(src, cfg.bytes, cfg.salt, prev), 0, DiagCandidate::Generation, prev);
+    if (next != prev) add(generation_seed(src, cfg.bytes, cfg.salt, next), 0, DiagCandidate::Generation, next);
+  }
+  if (op_bytes && op_bytes < cfg.bytes && op_bytes % 16 == 0) {
+    const uint64_t own = generation_seed(src, cfg.bytes, cfg.salt, g);
+    add(own, static_cast<int64_t>(op_bytes), DiagCandidate::Offset, 0);
+    add(own, -static_cast<int64_t>(op_bytes), DiagCandidate::Offset, 0);
+  }
+  std::vector<int> seen{src};
+  for (int other : ops.recv_from) {
+    if (std::find(seen.begin(), seen.end(), other) != seen.end()) continue;
+    seen.push_back(other);
+    add(generation_seed(other, cfg.bytes, cfg.salt, g), 0, DiagCandidate::Sender, other);
+  }
+  return c;
+}
+
+// This rank's findings as text, one "S" line per slot and one "E" line per
+// extent (parse_findings reads them back on every rank).
+std::string diagnose_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buffers& bufs, int gens,
+                           size_t op_bytes, const std::vector<uint64_t>& job_bad) {
+  const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
+  const int per = std::max(1, phase.max_recv_slots());
+  const size_t nrecv = ops.recv_from.size();
+  std::string out;
+  int done = 0;
+  for (size_t k = 0; k < job_bad.size() && done < cfg.diagnose; ++k) {
+    if (!job_bad[k]) continue;
+    ++done;
+    const int g = static_cast<int>(k / nrecv), i = static_cast<int>(k % nrecv);
+    const int src = ops.recv_from[static_cast<size_t>(i)];
+    const std::vector<DiagCandidate> cands = slot_candidates(ops, cfg, src, g, gens, op_bytes);
+    const std::vector<DiagExtent> ext =
+        t.diagnose(bufs.recv_buf(g * per + i), cfg.bytes, generation_seed(src, cfg.bytes, cfg.salt, g), cands);
+    const size_t kept = std::min<size_t>(ext.size(), kMaxDiagExtents);
+    uint64_t more_words = 0;
+    for (size_t e = kept; e < ext.size(); ++e) more_words += ext[e].words();
+    out += strfmt("S %d %d %d %zu %llu %zu\n", src, t.rank(), g, ext.size() - kept,
+                  static_cast<unsigned long long>(more_words), kept);
+    for (size_t e = 0; e < kept; ++e) {
+      const DiagExtent& x = ext[e];
+      out += strfmt("E %llu %llu %llu %llu %llu", static_cast<unsigned long long>(x.begin),
+                    static_cast<unsigned long long>(x.end), static_cast<unsigned long long>(x.zero),
+                    static_cast<unsigned long long>(x.other), static_cast<unsigned long long>(x.flipped_bits));
+      for (uint64_t c : x.cand) out += strfmt(" %llu", static_cast<unsigned long long>(c));
+      out += "\t" + describe_extent(x, cfg.bytes, cands.data(), static_cast<int>(cands.size())) + "\n";
+    }
+  }
+  return out;
+}
+
+void parse_findings(const std::string& text, std::vector<SlotDiagnosis>* out) {
+  size_t at = 0;
+  while (at < text.size()) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    const std::string line = text.substr(at, nl - at);
+    at = nl + 1;
+    if (line.rfind("S ", 0) == 0) {
+      SlotDiagnosis s;
+      unsigned long long more_e = 0, more_w = 0, kept = 0;
+      P2P_CHECK(std::sscanf(line.c_str(), "S %d %d %d %llu %llu %llu", &s.src, &s.dst, &s.gen, &more_e, &more_w, &kept) == 6,
+                "malformed diagnosis record: " + line);
+      s.more_extents = more_e;
+      s.more_words = more_w;
+      out->push_back(s);
+    } else if (line.rfind("E ", 0) == 0 && !out->empty()) {
+      const size_t tab = line.find('\t');
+      unsigned long long v[5 + kMaxDiagCandidates] = {0};
+      P2P_CHECK(tab != std::string::npos &&
+                    std::sscanf(line.c_str(), "E %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu", &v[0], &v[1],
+                                &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9], &v[10]) == 11,
+                "malformed diagnosis record: " + line);
+      DiagExtent x;
+      x.begin = v[0];
+      x.end = v[1];
+      x.zero = v[2];
+      x.other = v[3];
+      x.flipped_bits = v[4];
+      for (int k = 0; k < kMaxDiagCandidates; ++k) x.cand[k] = v[5 + k];
+      out->back().extents.push_back(x);
+      out->back().text.push_back(line.substr(tab + 1));
+    }
+  }
+}
+
+void print_findings(const PhaseResult& res) {
+  for (const SlotDiagnosis& s : res.diagnosis) {
+    const std::string head = strfmt("[p2p] diagnose %s %d->%d gen %d:", res.label.c_str(), s.src, s.dst, s.gen);
+    for (const std::string& line : s.text) std::fprintf(stderr, "%s %s\n", head.c_str(), line.c_str());
+    if (s.more_extents)
+      std::fprintf(stderr, "%s %llu more extents with %llu wrong words\n", head.c_str(),
+                   static_cast<unsigned long long>(s.more_extents), static_cast<unsigned long long>(s.more_words));
+  }
+  std::fflush(stderr);
 }
 
 }  // namespace
@@ -514,7 +645,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   res.wall_seconds = w1 - w0;
   if (skip || skip_some) t.set_discard(false);
 
-  if (active) maybe_inject_fault(t, bufs, me, phase_index, cfg.bytes);
+  if (active) maybe_inject_fault(t, bufs, me, phase_index, cfg.bytes, phase, cfg.salt, gens);
 
   std::string err = t.async_error();
   if (!err.empty()) P2P_FATAL("transport reported an asynchronous error: " + err);
@@ -526,16 +657,23 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   std::vector<uint64_t> vr(static_cast<size_t>(maxslots) * 2, 0);
   const int timed_gens = std::min(gens, cfg.iters);
   uint64_t cover[2] = {0, 0};  // timed deliveries, verified deliveries (this rank)
+  std::vector<uint64_t> job_bad;  // wrong words per (generation, slot) of this rank
   if (active) {
     const uint64_t nrecv = phase.ranks[static_cast<size_t>(me)].recv_from.size();
     cover[0] = nrecv * static_cast<uint64_t>(cfg.iters);
     if (cfg.verify) {
-      check_slots(t, phase, cfg, bufs, timed_gens, &vr);
+      check_slots(t, phase, cfg, bufs, timed_gens, &vr, &job_bad);
       cover[1] = nrecv * static_cast<uint64_t>(timed_gens);
     }
   }
   res.timed_msgs = boot.allreduce_sum_u64(cover[0]);
   res.verified_msgs = boot.allreduce_sum_u64(cover[1]);
+  // Collective whenever it is on: a rank without wrong words sends nothing.
+  if (cfg.verify && cfg.diagnose > 0) {
+    const std::string mine = diagnose_slots(t, phase, cfg, bufs, gens, res.op_bytes, job_bad);
+    for (const std::string& s : boot.allgather_string(mine)) parse_findings(s, &res.diagnosis);
+    if (me == 0) print_findings(res);
+  }
 
   res.rank_seconds = boot.allgather_value(my_seconds);
   const double span[2] = {w0, w1};

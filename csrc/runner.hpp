@@ -57,6 +57,23 @@ struct RunConfig {
   // RCCL's half-delivery.  P2P_RECHUNK=0 turns it off, so the timed check
   // reports the loss instead.
   bool rechunk = true;
+  // With verify: after the timed check, a rank whose slots had wrong words
+  // diagnoses its first `diagnose` failing (generation, slot) pairs
+  // (Transport::diagnose; PhaseResult::diagnosis).  0: off, nothing changes.
+  int diagnose = 0;
+};
+
+// What the diagnosis found in one receive slot of one generation: at most
+// kMaxDiagExtents extents, each with its one-line text (describe_extent), and
+// how much more there was.
+constexpr int kMaxDiagExtents = 8;
+struct SlotDiagnosis {
+  int src = -1, dst = -1;
+  int gen = 0;
+  std::vector<DiagExtent> extents;
+  std::vector<std::string> text;  // one per extent
+  uint64_t more_extents = 0;      // extents beyond the ones kept
+  uint64_t more_words = 0;        // their damaged words
 };
 
 struct FlowResult {
@@ -100,6 +117,9 @@ struct PhaseResult {
   // Wrong words the warmup still had after the last re-chunking (0: the
   // smaller ops fixed it).  Non-zero: the loss does not follow the op size.
   uint64_t warmup_residual = 0;
+  // RunConfig::diagnose: every rank's findings (rank order), empty when
+  // nothing was wrong or nothing was asked for.
+  std::vector<SlotDiagnosis> diagnosis;
 };
 
 // Send buffer + receive slots for one rank.  The slots are carved from one

@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "diagnose.hpp"
 #include "prng.hpp"
 
 namespace p2p {
@@ -65,6 +66,14 @@ class Transport {
     out.reserve(jobs.size());
     for (const auto& j : jobs) out.push_back(verify(j.p, j.bytes, j.seed));
     return out;
+  }
+  // Blocking: where `bytes` at p differ from the PRNG stream `seed` and what
+  // the wrong words hold instead (diagnose.hpp), as extents; at most
+  // kMaxDiagCandidates candidates.  GPU transports run the gfx950 kernel on
+  // their stream and read the records back once; the default knows nothing.
+  virtual std::vector<DiagExtent> diagnose(const void* /*p*/, size_t /*bytes*/, uint64_t /*seed*/,
+                                           const std::vector<DiagCandidate>& /*candidates*/) {
+    return {};
   }
 
   // ---- data plane: one group == one fused launch ----
@@ -286,5 +295,9 @@ std::unique_ptr<Transport> make_shm_transport(Bootstrap& boot, const TransportOp
 // host transport use it).
 VerifyResult host_verify(const void* p, size_t bytes, uint64_t seed);
 void host_fill(void* p, size_t bytes, uint64_t seed);
+// Transport::diagnose of the CPU transports: host_diagnose at the default
+// granule, merged into extents.
+std::vector<DiagExtent> host_diagnose_extents(const void* p, size_t bytes, uint64_t seed,
+                                              const std::vector<DiagCandidate>& candidates);
 
 }  // namespace p2p

@@ -159,6 +159,10 @@ class HostTransport final : public Transport {
   void fill(void* p, size_t bytes, uint64_t seed) override { host_fill(p, bytes, seed); }
   void zero(void* p, size_t bytes) override { std::memset(p, 0, bytes); }
   VerifyResult verify(const void* p, size_t bytes, uint64_t seed) override { return host_verify(p, bytes, seed); }
+  std::vector<DiagExtent> diagnose(const void* p, size_t bytes, uint64_t seed,
+                                   const std::vector<DiagCandidate>& candidates) override {
+    return host_diagnose_extents(p, bytes, seed, candidates);
+  }
 
   void group_begin() override {
     P2P_CHECK(!in_group_, "nested group");

@@ -214,6 +214,15 @@ class IpcTransport final : public Transport {
       return Transport::verify_many(jobs);
     return batch_verify(batch_, jobs, stream_, [this] { sync(); });
   }
+  // The diagnosis kernel and one readback of its records, behind the same
+  // bounded, abort-aware wait.
+  std::vector<DiagExtent> diagnose(const void* p, size_t bytes, uint64_t seed,
+                                   const std::vector<DiagCandidate>& candidates) override {
+    const size_t granule =
+        diag_.enqueue(p, bytes, seed, candidates.data(), static_cast<int>(candidates.size()), 0, stream_);
+    sync();
+    return merge_extents(diag_.records(), diag_.count(), bytes, granule);
+  }
 
   // Buffer sets are registered collectively in the same order on every rank,
   // so "the same set" on a peer is the one with the same position.  A receive
@@ -854,6 +863,7 @@ class IpcTransport final : public Transport {
   dev::VerifyAccum* acc_ = nullptr;
   dev::VerifyAccum* acc_host_ = nullptr;
   dev::BatchVerifier batch_;
+  dev::Diagnoser diag_;
   dev::VerifyImpl verify_impl_ = dev::VerifyImpl::Auto;
   std::string desc_;
   std::vector<Registration> regs_;

@@ -247,6 +247,17 @@ class RcclTransport final : public Transport {
     return batch_verify(batch_, jobs, stream_, [this] { sync(); });
   }
 
+  // The diagnosis kernel and one readback of its records on the buffer
+  // stream, behind the same bounded, abort-aware wait as the checks above.
+  std::vector<DiagExtent> diagnose(const void* p, size_t bytes, uint64_t seed,
+                                   const std::vector<DiagCandidate>& candidates) override {
+    buffer_work();
+    const size_t granule =
+        diag_.enqueue(p, bytes, seed, candidates.data(), static_cast<int>(candidates.size()), 0, stream_);
+    sync();
+    return merge_extents(diag_.records(), diag_.count(), bytes, granule);
+  }
+
   void group_begin() override {
     check_live("group_begin");
     nccl_ok(ncclGroupStart(), "ncclGroupStart");
@@ -1001,6 +1012,7 @@ class RcclTransport final : public Transport {
   dev::VerifyAccum* acc_ = nullptr;
   dev::VerifyAccum* acc_host_ = nullptr;
   dev::BatchVerifier batch_;
+  dev::Diagnoser diag_;
   dev::VerifyImpl verify_impl_ = dev::VerifyImpl::Auto;
   std::string desc_;
   int hook_ = 0;

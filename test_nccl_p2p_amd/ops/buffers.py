@@ -143,6 +143,136 @@ def reference_verify(data: torch.Tensor, seed: int) -> VerifyResult:
     return VerifyResult(int(bad.numel()), csum, first)
 
 
+# ---------------------------------------------------------------- diagnosis --
+
+class GranuleRecord(NamedTuple):
+    """One damaged granule (csrc/diagnose.hpp DiagRecord)."""
+    index: int         # granule number: bytes [index * granule, (index + 1) * granule)
+    first_bad: int     # byte offset of its first damaged word
+    last_bad: int      # byte offset of its last damaged word
+    zero: int          # words still poison
+    other: int         # words that match nothing
+    flipped_bits: int  # popcount(got ^ expected) over the `other` words
+    cand0: int = 0     # words that match candidate k
+    cand1: int = 0
+    cand2: int = 0
+    cand3: int = 0
+    cand4: int = 0
+    cand5: int = 0
+
+
+class Extent(NamedTuple):
+    """A maximal run of consecutive damaged granules with the same classes."""
+    begin: int         # byte offset of its first damaged word
+    end: int           # byte offset after its last damaged word (clipped to the buffer)
+    zero: int
+    other: int
+    flipped_bits: int
+    cand0: int = 0
+    cand1: int = 0
+    cand2: int = 0
+    cand3: int = 0
+    cand4: int = 0
+    cand5: int = 0
+
+
+def _candidates(candidates):
+    out = []
+    for c in candidates:
+        c = tuple(c)
+        out.append((int(c[0]) & (2**64 - 1), int(c[1])) + tuple(int(x) for x in c[2:]))
+    return out
+
+
+def diagnose_records(t: torch.Tensor, seed: int, candidates=(), granule: int = 0,
+                     stream: Optional[torch.cuda.Stream] = None, *, max_grid: int = 0):
+    """The gfx950 diagnosis kernel on ``t`` (blocking): its damaged granules
+    as :class:`GranuleRecord`.  ``candidates``: up to 6 ``(seed, shift)`` with
+    ``shift`` a signed byte count, a multiple of 16."""
+    nbytes = _check_tensor(t)
+    recs = require_native().diagnose(t.data_ptr(), nbytes, seed & (2**64 - 1), _candidates(candidates), granule,
+                                     _stream(stream), max_grid)
+    return [GranuleRecord(*r) for r in recs]
+
+
+def diagnose(t: torch.Tensor, seed: int, candidates=(), granule: int = 0,
+             stream: Optional[torch.cuda.Stream] = None, *, max_grid: int = 0):
+    """Where ``t`` differs from PRNG stream ``seed`` and what the wrong words
+    hold instead, as :class:`Extent` (``_p2pcore.describe_extent`` gives the
+    text of one)."""
+    nbytes = _check_tensor(t)
+    recs = diagnose_records(t, seed, candidates, granule, stream, max_grid=max_grid)
+    return [Extent(*e) for e in require_native().merge_extents([tuple(r) for r in recs], nbytes, granule)]
+
+
+def _popcount32(x: torch.Tensor) -> torch.Tensor:
+    x = x - ((x >> 1) & 0x55555555)
+    x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+    x = (x + (x >> 4)) & 0x0F0F0F0F
+    return ((x * 0x01010101) & M32) >> 24
+
+
+def reference_diagnose(data: torch.Tensor, seed: int, candidates=(), granule: int = 4096, start: int = 0):
+    """PyTorch implementation of the diagnosis contract (csrc/diagnose.hpp) on
+    a uint8 tensor, on top of :func:`reference_words`: the damaged granules as
+    :class:`GranuleRecord`.  ``data`` may be the slice of a larger buffer that
+    begins ``start`` bytes into it (a multiple of ``granule``) and runs to
+    its end; indices and offsets are then those of the whole buffer."""
+    assert granule >= 4096 and granule & (granule - 1) == 0 and start % granule == 0
+    data = data.reshape(-1).to(torch.uint8)
+    dev = data.device
+    nbytes = data.numel()
+    nwords = (nbytes + 3) // 4
+    if not nwords:
+        return []
+    pad = nwords * 4 - nbytes
+    d = torch.cat([data, torch.zeros(pad, dtype=torch.uint8, device=dev)]).to(torch.int64).reshape(nwords, 4)
+    mask = torch.full((nwords,), M32, dtype=torch.int64, device=dev)
+    if pad:
+        mask[-1] = (1 << (8 * (4 - pad))) - 1
+    got = (d[:, 0] | (d[:, 1] << 8) | (d[:, 2] << 16) | (d[:, 3] << 24)) & mask
+    w0 = start // 4
+    want = reference_words(w0, nwords, seed, dev) & mask
+    bad = got != want
+    zero = bad & (got == 0)
+    left = bad & ~zero                      # wrong, not poison, no candidate matched yet
+    classes = [zero]
+    cands = _candidates(candidates)
+    assert len(cands) <= 6
+    for cseed, shift, *_ in cands:
+        assert shift % 16 == 0
+        first = w0 + shift // 4             # stream index the slice's word 0 is compared with
+        skip = min(max(-first, 0), nwords)  # words whose shifted index is negative
+        cw = torch.zeros(nwords, dtype=torch.int64, device=dev)
+        if skip < nwords:
+            cw[skip:] = reference_words(first + skip, nwords - skip, cseed, dev)
+        valid = torch.arange(nwords, device=dev) >= skip
+        hit = left & valid & (got == (cw & mask))
+        classes.append(hit)
+        left = left & ~hit
+    classes += [torch.zeros_like(bad)] * (6 - len(cands))
+    flipped = torch.where(left, _popcount32(got ^ want), torch.zeros_like(got))
+    offs = start + 4 * torch.arange(nwords, dtype=torch.int64, device=dev)
+    gran = (offs - start) // granule
+    ngran = int(gran[-1].item()) + 1
+
+    def per_granule(x):
+        return torch.zeros(ngran, dtype=torch.int64, device=dev).index_add_(0, gran, x.to(torch.int64))
+
+    sums = [per_granule(c) for c in classes] + [per_granule(left), per_granule(flipped)]
+    big = torch.iinfo(torch.int64).max
+    first_bad = torch.full((ngran,), big, dtype=torch.int64, device=dev).scatter_reduce_(
+        0, gran[bad], offs[bad], "amin")
+    last_bad = torch.full((ngran,), -1, dtype=torch.int64, device=dev).scatter_reduce_(
+        0, gran[bad], offs[bad], "amax")
+    rows = torch.stack(sums + [first_bad, last_bad], dim=1).cpu().tolist()  # one transfer
+    out = []
+    for g, c in enumerate(rows):
+        if c[10] >= 0:
+            out.append(GranuleRecord(start // granule + g, c[9], c[10], c[0], c[7], c[8], *c[1:7]))
+    return out
+
+
 def payload_seed(src: int, nbytes: int, salt: int = 0) -> int:
     """Seed of the payload rank ``src`` sends (csrc/prng.hpp payload_seed)."""
     s = 0x9E3779B97F4A7C15 ^ ((src & M32) << 40) ^ nbytes ^ ((salt * 0xD6E8FEB86659FD93) & (2**64 - 1))
