@@ -190,5 +190,14 @@ struct SignalArgs {
 };
 void launch_signal(const SignalArgs& args, hipStream_t stream);
 
+// ---- what both kernels spin on and count in (pingpong.hip) ----
+// Memory for flags a wave spins on: uncached device memory when the runtime
+// allows it, so the spinning wave reads HBM rather than a stale line; plain
+// hipMalloc otherwise.  *uncached (if given) says which one it became.
+hipError_t alloc_signal_page(void** p, size_t bytes, bool* uncached = nullptr);
+// Ticks per second of the clock the deadlines and stamps count in
+// (s_memrealtime), as the device reports it; 0 if it reports none.
+double wall_clock_hz(int device);
+
 }  // namespace dev
 }  // namespace p2p

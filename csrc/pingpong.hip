@@ -124,5 +124,19 @@ void launch_pingpong(const PingRole& a, const PingRole* b, hipStream_t stream) {
   hipLaunchKernelGGL(pingpong_kernel, dim3(1), dim3(b ? 128 : 64), 0, stream, a, second);
 }
 
+hipError_t alloc_signal_page(void** p, size_t bytes, bool* uncached) {
+  if (uncached) *uncached = true;
+  if (hipExtMallocWithFlags(p, bytes, hipDeviceMallocUncached) == hipSuccess) return hipSuccess;
+  (void)hipGetLastError();
+  if (uncached) *uncached = false;
+  return hipMalloc(p, bytes);
+}
+
+double wall_clock_hz(int device) {
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess) return 0.0;
+  return khz > 0 ? khz * 1e3 : 0.0;
+}
+
 }  // namespace dev
 }  // namespace p2p

@@ -7,7 +7,9 @@
 // the p2p_matrix executable share one result schema.
 //
 // The fill / verify kernels are also exposed on raw device pointers so they
-// can be driven on torch tensors and checked against a PyTorch reference.
+// can be driven on torch tensors and checked against a PyTorch reference; so
+// are the one-wave ping-pong and signal kernels, with the two kinds of memory
+// they spin on (signal_page, HostWords), for tests against a protocol model.
 #include <hip/hip_runtime.h>
 
 #include <pybind11/pybind11.h>
@@ -464,6 +466,154 @@ std::string describe_extent_py(const py::tuple& t, size_t bytes, const std::vect
   return describe_extent(e, bytes, c.data(), static_cast<int>(c.size()));
 }
 
+// ---- the ping-pong and signal kernels on raw pointers (pingpong.hip) ----
+// Launch only, like copy and verify_launch; every argument is checked before
+// anything touches the device, so a bad call raises ValueError and launches
+// nothing.
+uintptr_t pointer_arg(uintptr_t p, size_t align, const char* what) {
+  if (!p) throw py::value_error(strfmt("%s is a null pointer", what));
+  if (p % align) throw py::value_error(strfmt("%s must be %zu-byte aligned", what, align));
+  return p;
+}
+
+using FlagList = std::vector<std::pair<uintptr_t, uint64_t>>;
+
+// Entries past the lists do not stay null: they point at trap_flag, with a
+// post value that shows (0xDEAD) and a wait value no flag reaches, so a
+// kernel that went past nposts / nwaits leaves a wrong word or an expired
+// deadline behind, not a fault.  Without a trap flag both lists must be full.
+dev::SignalArgs signal_args(const FlagList& posts, const FlagList& waits, uintptr_t status, uint64_t timeout_ticks,
+                            bool release_first, uintptr_t trap_flag) {
+  constexpr size_t kMax = static_cast<size_t>(dev::kMaxSignals);
+  if (posts.size() > kMax || waits.size() > kMax)
+    throw py::value_error(strfmt("signal: at most %d posts and %d waits", dev::kMaxSignals, dev::kMaxSignals));
+  if (!trap_flag && (posts.size() != kMax || waits.size() != kMax))
+    throw py::value_error(strfmt("signal: without a trap_flag all %d posts and all %d waits must be given",
+                                 dev::kMaxSignals, dev::kMaxSignals));
+  if (trap_flag) pointer_arg(trap_flag, 8, "signal: trap_flag");
+  dev::SignalArgs a{};
+  for (size_t i = 0; i < kMax; ++i) {
+    const bool post = i < posts.size(), wait = i < waits.size();
+    a.post_flag[i] = reinterpret_cast<unsigned long long*>(post ? pointer_arg(posts[i].first, 8, "signal: a post flag")
+                                                                : trap_flag);
+    a.post_value[i] = post ? posts[i].second : 0xDEADull;
+    a.wait_flag[i] = reinterpret_cast<const unsigned long long*>(
+        wait ? pointer_arg(waits[i].first, 8, "signal: a wait flag") : trap_flag);
+    a.wait_value[i] = wait ? waits[i].second : ~0ull;
+  }
+  a.nposts = static_cast<int>(posts.size());
+  a.nwaits = static_cast<int>(waits.size());
+  a.release_first = release_first ? 1 : 0;
+  a.status = reinterpret_cast<unsigned int*>(pointer_arg(status, 4, "signal: status_ptr"));
+  a.timeout_ticks = timeout_ticks;
+  return a;
+}
+
+// A role is a dict of the PingRole fields (or what dict() accepts, or a
+// named tuple); base, in_base, leader and stamps default to 0, and only a
+// leader needs stamps.
+dev::PingRole ping_role_arg(const py::object& role) {
+  py::dict d;
+  if (py::isinstance<py::dict>(role))
+    d = role.cast<py::dict>();
+  else if (py::hasattr(role, "_asdict"))
+    d = py::dict(role.attr("_asdict")());
+  else
+    d = py::dict(role);
+  static const char* const kFields[] = {"out_flag", "out_payload", "in_flag", "in_payload", "bytes",  "base",
+                                        "in_base",  "iters",       "leader",  "stamps",     "status", "timeout_ticks"};
+  for (const auto& kv : d) {
+    const std::string key = py::str(kv.first);
+    bool known = false;
+    for (const char* f : kFields) known = known || key == f;
+    if (!known) throw py::value_error("pingpong: a role has no field '" + key + "'");
+  }
+  auto get = [&d](const char* key, bool required) -> uint64_t {
+    if (!d.contains(key)) {
+      if (required) throw py::value_error(strfmt("pingpong: a role needs '%s'", key));
+      return 0;
+    }
+    return d[key].cast<uint64_t>();
+  };
+  dev::PingRole r{};
+  r.bytes = get("bytes", true);
+  if (r.bytes < 16 || r.bytes % 16) throw py::value_error("pingpong: bytes must be a multiple of 16, at least 16");
+  const long long iters = d.contains("iters") ? d["iters"].cast<long long>() : 0;
+  if (iters < 1 || iters > INT32_MAX) throw py::value_error("pingpong: iters must be at least 1");
+  r.iters = static_cast<int>(iters);
+  r.leader = get("leader", false) ? 1 : 0;
+  r.base = get("base", false);
+  r.in_base = get("in_base", false);
+  r.timeout_ticks = get("timeout_ticks", true);
+  r.out_flag = reinterpret_cast<unsigned long long*>(pointer_arg(get("out_flag", true), 8, "pingpong: out_flag"));
+  r.out_payload = reinterpret_cast<unsigned char*>(pointer_arg(get("out_payload", true), 16, "pingpong: out_payload"));
+  r.in_flag = reinterpret_cast<const unsigned long long*>(pointer_arg(get("in_flag", true), 8, "pingpong: in_flag"));
+  r.in_payload = reinterpret_cast<const unsigned char*>(pointer_arg(get("in_payload", true), 16, "pingpong: in_payload"));
+  r.status = reinterpret_cast<unsigned int*>(pointer_arg(get("status", true), 4, "pingpong: status"));
+  const uintptr_t stamps = get("stamps", false);
+  if (r.leader || stamps) pointer_arg(stamps, 8, "pingpong: stamps");
+  r.stamps = reinterpret_cast<unsigned long long*>(stamps);
+  return r;
+}
+
+void launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) P2P_FATAL(strfmt("%s: launch failed: %s", what, hipGetErrorString(e)));
+}
+
+// One allocation made as the transports make their signal pages.
+class SignalPage {
+ public:
+  explicit SignalPage(size_t bytes) : bytes_(bytes) {
+    if (!bytes) throw py::value_error("signal_page: bytes must be positive");
+    const hipError_t e = dev::alloc_signal_page(&p_, bytes, &uncached_);
+    if (e != hipSuccess) P2P_FATAL(strfmt("signal_page: allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e)));
+  }
+  SignalPage(const SignalPage&) = delete;
+  SignalPage& operator=(const SignalPage&) = delete;
+  ~SignalPage() {
+    if (p_) (void)hipFree(p_);
+  }
+  uintptr_t ptr() const { return reinterpret_cast<uintptr_t>(p_); }
+  size_t bytes() const { return bytes_; }
+  bool uncached() const { return uncached_; }
+
+ private:
+  void* p_ = nullptr;
+  size_t bytes_;
+  bool uncached_ = false;
+};
+
+// n 64-byte lines of fine-grained (coherent) pinned host memory, the stream
+// gate's kind: what the host writes while a kernel spins on it.
+class HostWords {
+ public:
+  static constexpr size_t kLine = 64;
+  explicit HostWords(size_t n) : n_(n) {
+    if (!n) throw py::value_error("HostWords: at least one line");
+    const hipError_t e = hipHostMalloc(&p_, n * kLine, hipHostMallocCoherent);
+    if (e != hipSuccess) P2P_FATAL(strfmt("HostWords: hipHostMalloc failed: %s", hipGetErrorString(e)));
+    for (size_t i = 0; i < n; ++i) store(i, 0);
+  }
+  HostWords(const HostWords&) = delete;
+  HostWords& operator=(const HostWords&) = delete;
+  ~HostWords() {
+    if (p_) (void)hipHostFree(p_);
+  }
+  size_t size() const { return n_; }
+  uintptr_t ptr(size_t i) const { return reinterpret_cast<uintptr_t>(line(i)); }
+  uint64_t load(size_t i) const { return __atomic_load_n(line(i), __ATOMIC_ACQUIRE); }
+  void store(size_t i, uint64_t v) { __atomic_store_n(line(i), v, __ATOMIC_RELEASE); }
+
+ private:
+  uint64_t* line(size_t i) const {
+    if (i >= n_) throw py::index_error(strfmt("HostWords: line %zu of %zu", i, n_));
+    return reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(p_) + i * kLine);
+  }
+  void* p_ = nullptr;
+  size_t n_;
+};
+
 py::list schedule_py(const std::string& mode, const std::string& dir, int n) {
   Schedule s = make_schedule(parse_mode(mode), parse_direction(dir), n);
   py::list phases;
@@ -655,6 +805,43 @@ PYBIND11_MODULE(_p2pcore, m) {
       }, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0,
       "The copy kernel over several (dst, src, bytes) ops, as the IPC transport launches a group's receives "
       "(max_blocks > 0: the ops of a launch share that many workgroups and grid-stride).");
+  m.attr("MAX_SIGNALS") = dev::kMaxSignals;
+  m.def("signal", [](const FlagList& posts, const FlagList& waits, uintptr_t status_ptr, uint64_t timeout_ticks,
+                     bool release_first, uintptr_t stream, uintptr_t trap_flag) {
+        const dev::SignalArgs a = signal_args(posts, waits, status_ptr, timeout_ticks, release_first, trap_flag);
+        dev::launch_signal(a, as_stream(stream));
+        launched("signal");
+      }, py::arg("posts"), py::arg("waits"), py::arg("status_ptr"), py::arg("timeout_ticks"),
+      py::arg("release_first") = false, py::arg("stream") = 0, py::arg("trap_flag") = 0,
+      "The one-wave signal kernel (launch only): posts and waits are lists of (flag_ptr, value), at most MAX_SIGNALS "
+      "each; bit 0 of the 32-bit word at status_ptr is set if a wait passed timeout_ticks.  Unused entries point at "
+      "trap_flag (post value 0xDEAD, wait value 2**64-1); with trap_flag 0 both lists must be full.");
+  m.def("pingpong", [](const py::object& a, const py::object& b, uintptr_t stream) {
+        const dev::PingRole ra = ping_role_arg(a);
+        dev::PingRole rb{};
+        if (!b.is_none()) rb = ping_role_arg(b);
+        dev::launch_pingpong(ra, b.is_none() ? nullptr : &rb, as_stream(stream));
+        launched("pingpong");
+      }, py::arg("a"), py::arg("b") = py::none(), py::arg("stream") = 0,
+      "The ping-pong kernel (launch only): role a as one wave, or a and b as the two waves of one workgroup.  A role "
+      "is a dict of out_flag, out_payload, in_flag, in_payload, bytes, base, in_base, iters, leader, stamps, status, "
+      "timeout_ticks (pointers as integers).");
+  m.def("wall_clock_hz", []() {
+        int dv = 0;
+        if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
+        return dev::wall_clock_hz(dv);
+      }, "Ticks per second of the current device's wall clock, the unit of timeout_ticks and of the stamps.");
+  py::class_<SignalPage>(m, "signal_page")
+      .def(py::init<size_t>(), py::arg("bytes"))
+      .def_property_readonly("ptr", &SignalPage::ptr)
+      .def_property_readonly("bytes", &SignalPage::bytes)
+      .def_property_readonly("uncached", &SignalPage::uncached);
+  py::class_<HostWords>(m, "HostWords")
+      .def(py::init<size_t>(), py::arg("n"))
+      .def("__len__", &HostWords::size)
+      .def("ptr", &HostWords::ptr, py::arg("i"))
+      .def("load", &HostWords::load, py::arg("i"))
+      .def("store", &HostWords::store, py::arg("i"), py::arg("v"));
   m.def("fill_geometry", [](size_t bytes) {
     auto g = dev::fill_geometry(bytes);
     return py::make_tuple(g.grid, g.block, g.lds_bytes);

@@ -19,6 +19,12 @@ void StreamGate::arm(hipStream_t stream, double timeout_s) {
     __atomic_store_n(flag_, 0ull, __ATOMIC_RELEASE);
     HIPCHECK(hipMalloc(reinterpret_cast<void**>(&status_), sizeof(unsigned int)));
     HIPCHECK(hipMemsetAsync(status_, 0, sizeof(unsigned int), stream));
+    // The deadline counts in the device's own wall clock, asked for as the IPC
+    // transport asks for it.
+    int device = 0;
+    HIPCHECK(hipGetDevice(&device));
+    tick_hz_ = dev::wall_clock_hz(device);
+    P2P_CHECK(tick_hz_ > 0, "device reports no wall clock rate");
   }
   dev::SignalArgs a{};
   a.nposts = 0;
@@ -27,7 +33,7 @@ void StreamGate::arm(hipStream_t stream, double timeout_s) {
   a.wait_value[0] = ++seq_;
   a.release_first = 0;
   a.status = status_;
-  a.timeout_ticks = static_cast<unsigned long long>(timeout_s * 1e8);  // s_memrealtime: 100 MHz
+  a.timeout_ticks = static_cast<unsigned long long>(timeout_s * tick_hz_);
   dev::launch_signal(a, stream);
 }
 

@@ -23,6 +23,7 @@ class StreamGate {
   unsigned long long* flag_ = nullptr;  // host-pinned, written by the host only
   unsigned int* status_ = nullptr;      // device: bit 0 = a gate expired
   unsigned long long seq_ = 0;
+  double tick_hz_ = 0;                  // of the device the gate was first armed on
 };
 
 }  // namespace p2p

@@ -97,10 +97,8 @@ class IpcTransport final : public Transport {
     HIPCHECK(hipGetDeviceProperties(&prop, device_));
     desc_ = strfmt("hip:%d %s (%s, %d CUs) ipc-%s", device_, prop.name, prop.gcnArchName, prop.multiProcessorCount,
                    engine_.c_str());
-    int khz = 0;
-    HIPCHECK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_));
-    P2P_CHECK(khz > 0, "device reports no wall clock rate");
-    tick_hz_ = khz * 1e3;
+    tick_hz_ = dev::wall_clock_hz(device_);
+    P2P_CHECK(tick_hz_ > 0, "device reports no wall clock rate");
     if (const char* pc = std::getenv("P2P_IPC_POOL")) pool_cap_ = std::strcmp(pc, "0") ? parse_size(pc) : 0;
     if (const char* ir = std::getenv("P2P_INJECT_EXPORT_REFUSALS")) inject_refusals_ = std::atoi(ir);
     // HIP 7.0's hipIpcOpenMemHandle never returns for a block whose size mod
@@ -476,7 +474,7 @@ class IpcTransport final : public Transport {
   void pingpong_setup_once() {
     const size_t bytes = kPingSlot * static_cast<size_t>(n_ + 1);
     Export me{};
-    page_ = exportable(bytes, &me.handle, [&](void** q) { return alloc_signal_page(q, bytes); });
+    page_ = exportable(bytes, &me.handle, [&](void** q) { return dev::alloc_signal_page(q, bytes); });
     // Stream-ordered and waited for with the bounded sync(): a device-wide
     // synchronize would also wait, unbounded, for any other session's work.
     HIPCHECK(hipMemsetAsync(page_, 0, bytes, stream_));
@@ -770,7 +768,7 @@ class IpcTransport final : public Transport {
   void setup_sync_pages_once() {
     const size_t bytes = kSyncLine * 2 * static_cast<size_t>(n_);
     Export me{};
-    sync_page_ = exportable(bytes, &me.handle, [&](void** q) { return alloc_signal_page(q, bytes); });
+    sync_page_ = exportable(bytes, &me.handle, [&](void** q) { return dev::alloc_signal_page(q, bytes); });
     HIPCHECK(hipMemsetAsync(sync_page_, 0, bytes, stream_));
     sync();  // bounded (see pingpong_setup)
     HIPCHECK(hipHostMalloc(&sig_status_, 64, hipHostMallocMapped));
@@ -917,13 +915,6 @@ class IpcTransport final : public Transport {
     auto it = blocks_.find(p);
     P2P_CHECK(it != blocks_.end(), "ipc transport exports only buffers it allocated");
     return it->second.handle;
-  }
-  // Uncached device memory when the runtime allows it, so a spinning wave
-  // reads HBM rather than a stale line.
-  static hipError_t alloc_signal_page(void** q, size_t bytes) {
-    if (hipExtMallocWithFlags(q, bytes, hipDeviceMallocUncached) == hipSuccess) return hipSuccess;
-    (void)hipGetLastError();
-    return hipMalloc(q, bytes);
   }
   void drain_pool() {
     for (auto& b : pool_) (void)hipFree(b.first);

@@ -89,6 +89,68 @@ def test_chunking_is_rccl_only(native):
     assert sess.link_reports() == "[null]"
 
 
+def _ping_role(**changes):
+    """A role that passes every check (the addresses are never used: the
+    checks below raise before anything is launched)."""
+    role = dict(out_flag=0x1000, out_payload=0x1100, in_flag=0x2000, in_payload=0x2100, bytes=32, base=0, in_base=0,
+                iters=1, leader=1, stamps=0x3000, status=0x4000, timeout_ticks=1000)
+    role.update(changes)
+    return role
+
+
+@pytest.mark.parametrize("changes", [
+    dict(bytes=0), dict(bytes=8), dict(bytes=24), dict(bytes=4112 + 8), dict(iters=0), dict(iters=-1),
+    dict(out_flag=0), dict(out_payload=0), dict(in_flag=0), dict(in_payload=0), dict(status=0), dict(stamps=0),
+    dict(out_flag=0x1004), dict(in_payload=0x2108), dict(no_such_field=1),
+], ids=lambda c: "-".join("%s=%s" % kv for kv in c.items()))
+@pytest.mark.parametrize("second", [False, True], ids=["a", "b"])
+def test_pingpong_binding_refuses_bad_roles(native, changes, second):
+    """native.pingpong checks both roles before it launches: payload bytes a
+    multiple of 16 and at least 16, at least one iteration, no null or
+    misaligned pointer, no unknown field."""
+    bad = _ping_role(**changes)
+    with pytest.raises(ValueError):
+        if second:
+            native.pingpong(_ping_role(), bad)
+        else:
+            native.pingpong(bad)
+    missing = _ping_role()
+    del missing["bytes"]
+    with pytest.raises(ValueError):
+        native.pingpong(missing)
+
+
+def test_signal_binding_refuses_bad_lists(native):
+    """native.signal: at most MAX_SIGNALS posts and waits; without a trap flag
+    for the unused entries both lists must be full; no null or misaligned
+    flag, status or trap pointer.  Nothing is launched."""
+    n = native.MAX_SIGNALS
+    assert n == 16
+    flags = [(0x1000 + 128 * i, i) for i in range(n + 1)]
+    status, trap = 0x8000, 0x9000
+    for posts, waits, kw in [
+        (flags, [], dict(trap_flag=trap)),              # 17 posts
+        ([], flags, dict(trap_flag=trap)),              # 17 waits
+        (flags, flags, dict()),                         # 17 of each, no trap
+        (flags[:n], flags[:n - 1], dict()),             # an unused wait and no trap
+        (flags[:n - 1], flags[:n], dict()),             # an unused post and no trap
+        ([], [], dict()),
+        ([(0, 1)], [], dict(trap_flag=trap)),           # null post flag
+        ([], [(0, 1)], dict(trap_flag=trap)),           # null wait flag
+        ([(0x1004, 1)], [], dict(trap_flag=trap)),      # misaligned
+        ([], [], dict(trap_flag=trap + 4)),
+    ]:
+        with pytest.raises(ValueError):
+            native.signal(posts, waits, status, 1000, **kw)
+    with pytest.raises(ValueError):
+        native.signal(flags[:n], flags[:n], 0, 1000)    # null status
+    with pytest.raises(ValueError):
+        native.signal([], [], status + 2, 1000, trap_flag=trap)
+    for ctor in (native.signal_page, native.HostWords):
+        with pytest.raises(ValueError):
+            ctor(0)
+
+
 def test_child_dies_with_its_parent():
     """utils.proc: a child in a session of its own (out of reach of a kill of
     its parent's process group) that called die_with_parent() is killed by
