@@ -100,6 +100,12 @@ data
       --no-verify        zero-filled sends, nothing read back (the reference's data)
       --verify-impl I    auto (= lds8) | lds8 (alias lds) | stride (alias reg)
                          (LDS-DMA- or register-staged verify kernel)
+      --verify-inline    also check every timed delivery as the copy kernel moves it, inside
+                         the timed loop (implies --verify): coverage 1.0 at any size and
+                         iteration count, where the check after timing sees one delivery
+                         per receive generation.  It tests what the receiver loaded, not
+                         that the store landed, so the check after timing still runs.
+                         Only --transport ipc --ipc-engine kernel           [P2P_VERIFY_INLINE]
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -155,7 +161,8 @@ environment (recorded in every --json provenance record; docs/OUTPUT.md)
   P2P_HOSTNAME=name      hostname for the placement check (emulated hosts)
   P2P_DEVICE=N           default of --device
   P2P_DIAGNOSE=N         default of --diagnose
-  P2P_INJECT_FAULT=kind@rank[:phase]   corrupt | exit | hang | skip | skip-some | stale (tests)
+  P2P_VERIFY_INLINE=1    default of --verify-inline
+  P2P_INJECT_FAULT=kind@rank[:phase]   corrupt | corrupt-send | exit | hang | skip | skip-some | stale (tests)
   P2P_ROCTX=1, P2P_LOG=1 roctx ranges; engine log on stderr
 )";
 }
@@ -191,6 +198,8 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
   if (const char* d = std::getenv("P2P_DEVICE"); d && *d) cfg->device = std::atoi(d);
   // P2P_DIAGNOSE: the default of --diagnose.
   if (const char* d = std::getenv("P2P_DIAGNOSE"); d && *d) cfg->run.diagnose = std::max(0, std::atoi(d));
+  // P2P_VERIFY_INLINE=1: the default of --verify-inline.
+  if (const char* v = std::getenv("P2P_VERIFY_INLINE"); v && *v) cfg->run.inline_check = std::atoi(v) != 0;
   for (int i = 0; i < argc; ++i) {
     std::string a = argv[i];
     std::string val;
@@ -325,6 +334,9 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       cfg->run.verify = true;
     } else if (a == "--no-verify") {
       cfg->run.verify = false;
+    } else if (a == "--verify-inline") {
+      cfg->run.inline_check = true;
+      cfg->run.verify = true;
     } else if (a == "--diagnose") {
       cfg->run.diagnose = int_arg(0);
     } else if (a == "--verify-impl") {
@@ -409,6 +421,18 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
   if (cfg->device_latency && cfg->transport != "ipc") {
     std::fprintf(stderr, "p2p_matrix: --device-latency needs a one-sided transport (--transport ipc); %s has none\n",
                  cfg->transport.c_str());
+    *exit_code = 1;
+    return false;
+  }
+  // The inline check lives in the pull engine's own copy kernel; --no-verify
+  // (no payload to compare with) switches it off again.
+  if (!cfg->run.verify) cfg->run.inline_check = false;
+  if (cfg->run.inline_check && (cfg->transport != "ipc" || cfg->ipc_engine != "kernel")) {
+    std::fprintf(stderr,
+                 "p2p_matrix: --verify-inline checks deliveries inside the copy kernel of --transport ipc --ipc-engine "
+                 "kernel; %s%s%s moves them by other means\n",
+                 cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",
+                 cfg->transport == "ipc" ? cfg->ipc_engine.c_str() : "");
     *exit_code = 1;
     return false;
   }

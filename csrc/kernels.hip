@@ -630,7 +630,58 @@ struct CopyArgs {
 constexpr int kSystemCoherent = 1 | 16;
 constexpr int kRsrcFlags = 0x00020000;  // raw buffer descriptor word 3 for gfx950
 
-__global__ __launch_bounds__(kBlock) void multi_copy_kernel(const CopyArgs a) {
+// What the checked copy carries per op beyond CopyArgs, by value as well
+// (about 1.8 KiB of kernarg with CopyArgs: still a single stream operation).
+struct CopyCheckArgs {
+  uint64_t seed[kMaxCopyOps];
+  uint64_t stream_vec[kMaxCopyOps];  // stream_offset / 16, a multiple of kBlockVecs
+  CopyCheck* record[kMaxCopyOps];
+};
+struct CheckedCopyArgs {
+  CopyArgs copy;
+  CopyCheckArgs check;
+};
+
+// A lane's findings of the checked copy, committed once at the end.  The
+// clean path is one wave-wide vote: a wave without a wrong word does nothing
+// more -- no LDS, no barrier, no atomic.  A wave with one reduces over its 64
+// lanes and commits with one atomic per field; first_bad is in stream bytes.
+__device__ __forceinline__ void copy_check_commit(Partial acc, CopyCheck* record) {
+  if (__builtin_amdgcn_ballot_w64(acc.mism != 0) == 0) return;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    acc.mism += __shfl_xor(acc.mism, off, 64);
+    acc.first = min(acc.first, __shfl_xor(acc.first, off, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&record->mismatches, acc.mism);
+    atomicMin(&record->first_bad, acc.first);
+  }
+}
+
+// The sub-16-byte tail, one byte per lane (lanes 0..tail-1 of the op's first
+// workgroup, all in wave 0): `bad_byte` says whether this lane's loaded byte
+// differs from the stream's.  check_tail's rule on those bytes: a word is
+// wrong when any of its bytes present is (the final partial word masked to
+// them), and counts once.  Lane 0 takes the words' findings.
+__device__ __forceinline__ void copy_check_tail(bool bad_byte, uint64_t tail_offset, Partial& acc) {
+  const unsigned long long bytes = __builtin_amdgcn_ballot_w64(bad_byte);
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int w = 3; w >= 0; --w)
+    if ((bytes >> (4 * w)) & 0xFull) {
+      acc.mism += 1;
+      acc.first = min(acc.first, static_cast<unsigned long long>(tail_offset + 4 * w));
+    }
+}
+
+// One workgroup of the multi-source copy, plain (CHECKED = false, `k` unused)
+// or checked: the two share the workgroup -> op lookup and both access forms;
+// the checked one regenerates each loaded vector's expected value
+// (prng_vec_k, key block-uniform as in fill_grid_kernel) while the load is in
+// flight, compares by check_vec's rule, and stores what it loaded.
+template <bool CHECKED>
+__device__ __forceinline__ void copy_workgroup(const CopyArgs& a, const CopyCheckArgs* k) {
   // Workgroup -> op: block ranges are contiguous per op.  Every workgroup
   // moves a single 4 KiB chunk, so this lookup is on its critical path: a
   // linear scan of up to 16 dependent scalar loads cost 6% at 16 ops x 32 MiB
@@ -652,6 +703,23 @@ __global__ __launch_bounds__(kBlock) void multi_copy_kernel(const CopyArgs a) {
   const uint4* __restrict__ s = a.src[op];
   uint4* __restrict__ d = a.dst[op];
   const uint64_t n = a.nvec[op];
+  // Checked only: the op's stream, where its first vector sits in it, and
+  // this lane's findings.
+  [[maybe_unused]] uint64_t seed = 0, sv0 = 0;
+  [[maybe_unused]] Partial acc{0, 0, ~0ull};
+  [[maybe_unused]] bool bad_byte = false;
+  if constexpr (CHECKED) {
+    seed = k->seed[op];
+    sv0 = k->stream_vec[op];
+  }
+  // Checked only, once both loops are done: the tail's bytes sit in lanes
+  // 0..14 of the op's first workgroup; then the wave's vote and commit.
+  auto finish = [&] {
+    if constexpr (CHECKED) {
+      if (b == 0 && a.tail[op] && threadIdx.x < 64) copy_check_tail(bad_byte, (sv0 + n) * 16, acc);
+      copy_check_commit(acc, k->record[op]);
+    }
+  };
   if ((a.coherent >> op) & 1u) {
     // One descriptor pair per 4 KiB chunk (block-uniform base, lane offset in
     // voffset); the range check drops the lanes past the end of the op.
@@ -660,14 +728,22 @@ __global__ __launch_bounds__(kBlock) void multi_copy_kernel(const CopyArgs a) {
       auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(s + base), 0, bytes, kRsrcFlags);
       auto rd = __builtin_amdgcn_make_buffer_rsrc(d + base, 0, bytes, kRsrcFlags);
       const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, static_cast<int>(threadIdx.x) * 16, 0, kSystemCoherent);
+      if constexpr (CHECKED) {
+        const uint32_t key = prng_key(seed, (sv0 + base) * 4);  // block-uniform: scalar ALU
+        // A lane past the end loaded nothing (the descriptor returned 0).
+        if (static_cast<int>(threadIdx.x) * 16 < bytes)
+          check_vec<true>(make_uint4(v[0], v[1], v[2], v[3]), key, sv0 + base + threadIdx.x, acc);
+      }
       __builtin_amdgcn_raw_buffer_store_b128(v, rd, static_cast<int>(threadIdx.x) * 16, 0, kSystemCoherent);
     }
     if (b == 0 && threadIdx.x < a.tail[op]) {
       auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(s + n), 0, static_cast<int>(a.tail[op]), kRsrcFlags);
       auto rd = __builtin_amdgcn_make_buffer_rsrc(d + n, 0, static_cast<int>(a.tail[op]), kRsrcFlags);
       const auto v = __builtin_amdgcn_raw_buffer_load_b8(rs, static_cast<int>(threadIdx.x), 0, kSystemCoherent);
+      if constexpr (CHECKED) bad_byte = static_cast<uint8_t>(v) != prng_byte(seed, (sv0 + n) * 16 + threadIdx.x);
       __builtin_amdgcn_raw_buffer_store_b8(v, rd, static_cast<int>(threadIdx.x), 0, kSystemCoherent);
     }
+    finish();
     return;
   }
   // Device-local op: non-temporal load and store (3.25-3.28 TB/s of payload
@@ -675,12 +751,39 @@ __global__ __launch_bounds__(kBlock) void multi_copy_kernel(const CopyArgs a) {
   // profiles/r2_copy_nt/).
   const u32x4* __restrict__ sv = reinterpret_cast<const u32x4*>(s);
   u32x4* __restrict__ dv = reinterpret_cast<u32x4*>(d);
-  for (uint64_t i = static_cast<uint64_t>(b) * kBlockVecs + threadIdx.x; i < n; i += static_cast<uint64_t>(nb) * kBlockVecs)
-    __builtin_nontemporal_store(__builtin_nontemporal_load(sv + i), dv + i);
+  [[maybe_unused]] uint64_t base = static_cast<uint64_t>(b) * kBlockVecs;  // checked only: i without the lane, for the key
+  for (uint64_t i = static_cast<uint64_t>(b) * kBlockVecs + threadIdx.x; i < n; i += static_cast<uint64_t>(nb) * kBlockVecs) {
+    const u32x4 v = __builtin_nontemporal_load(sv + i);
+    if constexpr (CHECKED) {
+      const uint32_t key = prng_key(seed, (sv0 + base) * 4);  // block-uniform: scalar ALU
+      check_vec<true>(make_uint4(v.x, v.y, v.z, v.w), key, sv0 + i, acc);
+      base += static_cast<uint64_t>(nb) * kBlockVecs;
+    }
+    __builtin_nontemporal_store(v, dv + i);
+  }
   if (b == 0 && threadIdx.x < a.tail[op]) {
     const uint8_t* st = reinterpret_cast<const uint8_t*>(s + n);
     uint8_t* dt = reinterpret_cast<uint8_t*>(d + n);
-    dt[threadIdx.x] = st[threadIdx.x];
+    const uint8_t v = st[threadIdx.x];
+    if constexpr (CHECKED) bad_byte = v != prng_byte(seed, (sv0 + n) * 16 + threadIdx.x);
+    dt[threadIdx.x] = v;
+  }
+  finish();
+}
+
+__global__ __launch_bounds__(kBlock) void multi_copy_kernel(const CopyArgs a) { copy_workgroup<false>(a, nullptr); }
+
+// multi_copy_kernel that also checks every word it moves against the op's
+// PRNG stream (kernels.hpp CheckedCopyOp).
+__global__ __launch_bounds__(kBlock) void multi_copy_checked_kernel(const CheckedCopyArgs a) {
+  copy_workgroup<true>(a.copy, &a.check);
+}
+
+__global__ __launch_bounds__(kBlock) void copy_check_reset_kernel(CopyCheck* records, int n) {
+  const int i = static_cast<int>(blockIdx.x) * kBlock + static_cast<int>(threadIdx.x);
+  if (i < n) {
+    records[i].mismatches = 0;
+    records[i].first_bad = ~0ull;
   }
 }
 
@@ -688,10 +791,11 @@ __global__ __launch_bounds__(kBlock) void multi_copy_kernel(const CopyArgs a) {
 
 namespace {
 
-// One launch over at most kMaxCopyOps ops; with max_blocks == 0 the caller
+// CopyArgs of one launch over at most kMaxCopyOps ops (Op: CopyOp or
+// CheckedCopyOp); returns its workgroups.  With max_blocks == 0 the caller
 // keeps the total at or under kMaxGrid blocks, so every op gets a full grid.
-void launch_copy_group(const CopyOp* ops, int cnt, hipStream_t stream, int max_blocks) {
-  CopyArgs a{};
+template <class Op>
+uint32_t plan_copy_group(const Op* ops, int cnt, int max_blocks, CopyArgs& a) {
   a.nops = cnt;
   a.coherent = 0;
   uint64_t need[kMaxCopyOps] = {0};
@@ -719,16 +823,43 @@ void launch_copy_group(const CopyOp* ops, int cnt, hipStream_t stream, int max_b
   a.uniform = static_cast<int32_t>(a.block_begin[1] - a.block_begin[0]);
   for (int i = 1; i < cnt; ++i)
     if (a.block_begin[i + 1] - a.block_begin[i] != static_cast<uint32_t>(a.uniform)) a.uniform = 0;
-  multi_copy_kernel<<<acc, kBlock, 0, stream>>>(a);
+  return acc;
+}
+
+void launch_copy_group(const CopyOp* ops, int cnt, hipStream_t stream, int max_blocks) {
+  CopyArgs a{};
+  const uint32_t grid = plan_copy_group(ops, cnt, max_blocks, a);
+  multi_copy_kernel<<<grid, kBlock, 0, stream>>>(a);
+  HIP_OK(hipGetLastError());
+}
+
+void launch_copy_group(const CheckedCopyOp* ops, int cnt, hipStream_t stream, int max_blocks) {
+  CheckedCopyArgs a{};
+  const uint32_t grid = plan_copy_group(ops, cnt, max_blocks, a.copy);
+  for (int i = 0; i < cnt; ++i) {
+    a.check.seed[i] = ops[i].seed;
+    a.check.stream_vec[i] = ops[i].stream_offset / 16;
+    a.check.record[i] = ops[i].record;
+  }
+  multi_copy_checked_kernel<<<grid, kBlock, 0, stream>>>(a);
   HIP_OK(hipGetLastError());
 }
 
 uint64_t copy_blocks(size_t bytes) { return std::max<uint64_t>(1, (bytes / 16 + kBlockVecs - 1) / kBlockVecs); }
 
+// Bytes [off, off + n) of an op as an op of its own.
+CopyOp copy_piece(const CopyOp& o, size_t off, size_t n) {
+  return {static_cast<const char*>(o.src) + off, static_cast<char*>(o.dst) + off, n, o.coherent};
+}
+CheckedCopyOp copy_piece(const CheckedCopyOp& o, size_t off, size_t n) {
+  CheckedCopyOp p = o;
+  static_cast<CopyOp&>(p) = copy_piece(static_cast<const CopyOp&>(o), off, n);
+  p.stream_offset = o.stream_offset + off;  // pieces are multiples of 4 GiB apart: still 4 KiB aligned
+  return p;
+}
 
-}  // namespace
-
-void launch_multi_copy(const CopyOp* ops, int nops, hipStream_t stream, int max_blocks) {
+template <class Op>
+void launch_copy_ops(const Op* ops, int nops, hipStream_t stream, int max_blocks) {
   constexpr int max_ops = kMaxCopyOps;
   if (max_blocks > 0) {  // explicit grid cap (grid-shape experiments): the ops share it
     for (int first = 0; first < nops; first += max_ops)
@@ -740,13 +871,13 @@ void launch_multi_copy(const CopyOp* ops, int nops, hipStream_t stream, int max_
   // grid-stride pass over a capped grid streams ~5% slower (IPC self path:
   // 2.98 TB/s at 16-64 GiB vs 3.12 at 4 GiB, profiles/r1_sweeps).
   const size_t piece = static_cast<size_t>(kMaxGrid * kBlockVecs * 16);
-  std::vector<CopyOp> pieces;
+  std::vector<Op> pieces;
   for (int i = 0; i < nops; ++i) {
-    const CopyOp& o = ops[i];
+    const Op& o = ops[i];
     size_t off = 0;
     do {
       const size_t n = std::min(piece, o.bytes - off);
-      pieces.push_back({static_cast<const char*>(o.src) + off, static_cast<char*>(o.dst) + off, n, o.coherent});
+      pieces.push_back(copy_piece(o, off, n));
       off += n;
     } while (off < o.bytes);
   }
@@ -760,6 +891,26 @@ void launch_multi_copy(const CopyOp* ops, int nops, hipStream_t stream, int max_
     launch_copy_group(pieces.data() + i, static_cast<int>(j - i), stream, 0);
     i = j;
   }
+}
+
+}  // namespace
+
+void launch_multi_copy(const CopyOp* ops, int nops, hipStream_t stream, int max_blocks) {
+  launch_copy_ops(ops, nops, stream, max_blocks);
+}
+
+void launch_copy_check_reset(CopyCheck* records, int n, hipStream_t stream) {
+  if (n <= 0) return;
+  copy_check_reset_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(records, n);
+  HIP_OK(hipGetLastError());
+}
+
+void launch_multi_copy_checked(const CheckedCopyOp* ops, int nops, hipStream_t stream, int max_blocks) {
+  for (int i = 0; i < nops; ++i) {
+    P2P_CHECK(ops[i].stream_offset % 4096 == 0, "multi_copy_checked: stream_offset must be a multiple of 4096");
+    P2P_CHECK(ops[i].record != nullptr, "multi_copy_checked: every op needs a record");
+  }
+  launch_copy_ops(ops, nops, stream, max_blocks);
 }
 
 }  // namespace dev

@@ -21,7 +21,9 @@
 //             the 4 waves -> one atomic per block into one of kVerifyShards
 //             64-byte counters (no single hot address), then a one-wave
 //             finalize kernel folds the shards
-//   copy    — multi-source copy for the IPC transport (remote loads over xGMI)
+//   copy    — multi-source copy for the IPC transport (remote loads over xGMI),
+//             and its checked form: the same copy comparing every word it
+//             loads with the PRNG stream due, for the inline check
 //
 // Measured on MI355X (profiles/, scripts/fill_probe.hip): streaming at one
 // 16 B access per lane with one block per 4 KiB (a "full grid", up to 2^20
@@ -143,6 +145,34 @@ struct CopyOp {
 };
 constexpr int kMaxCopyOps = 32;  // ops per launch (one bit each in CopyArgs::coherent)
 void launch_multi_copy(const CopyOp* ops, int nops, hipStream_t stream, int max_blocks = 0);
+
+// ---- checked multi-source copy (inline verification of a pull) ----
+// The same copy (geometry, accesses, host-side splitting) whose every lane
+// also regenerates the word it expects and compares it with the one it
+// loaded, before storing that loaded value -- matched or not.  Op i's data
+// is bytes [stream_offset, stream_offset + bytes) of PRNG stream `seed`;
+// stream_offset must be a multiple of 4096 (a P2P_CHECK), so a workgroup's
+// 1024 words never straddle a 2^32-word key span.  Words and the tail follow
+// the verify kernels' rules (32-bit words, the final partial word masked).
+// A wave with no wrong word does nothing more (no LDS, no barrier, no
+// atomic); a wave with one reduces over its lanes and commits with one
+// atomicAdd and one atomicMin into the op's record, first_bad in stream
+// bytes (stream_offset + position).  Several ops may name one record: it
+// accumulates over ops and launches until launch_copy_check_reset.
+// What it proves: the value the receiver LOADED is the one due.  Whether the
+// store landed is the memory check's business (launch_verify).
+struct CopyCheck {
+  unsigned long long mismatches;  // wrong 32-bit words (a partial tail word counts once)
+  unsigned long long first_bad;   // lowest wrong stream byte offset, ~0 if none
+};
+struct CheckedCopyOp : CopyOp {
+  uint64_t seed = 0;
+  uint64_t stream_offset = 0;
+  CopyCheck* record = nullptr;  // device memory (hipMalloc)
+};
+// Stream-ordered: records [0, n) become {0, ~0}.
+void launch_copy_check_reset(CopyCheck* records, int n, hipStream_t stream);
+void launch_multi_copy_checked(const CheckedCopyOp* ops, int nops, hipStream_t stream, int max_blocks = 0);
 
 // ---- device-initiated ping-pong (pingpong.hip) ----
 // One wave per role.  The leader writes message i (payload words = base+i+1,

@@ -15,6 +15,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <memory>
@@ -106,7 +107,7 @@ class Session {
   // One (mode, dir, size) run; returns the run JSON (report.cpp schema).
   std::string run(const std::string& mode, const std::string& dir, size_t bytes, int iters, int warmup,
                   const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
-                  int diagnose) {
+                  int diagnose, bool inline_check) {
     Schedule s = make_schedule(parse_mode(mode), parse_direction(dir), world());
     restrict_cells(&s, cells, true);
     RunConfig cfg;
@@ -117,6 +118,9 @@ class Session {
     cfg.verify = verify;
     cfg.salt = ++salt_;
     cfg.diagnose = std::max(0, diagnose);
+    cfg.inline_check = inline_check;
+    P2P_CHECK(!inline_check || (verify && t_->supports_inline_check()),
+              "inline_check needs verify=True and transport 'ipc' or 'ipc:kernel' (the pull engine's own copy kernel)");
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
@@ -360,6 +364,86 @@ void device_verify_many_launch(const std::vector<std::tuple<uintptr_t, size_t, u
   std::vector<dev::VerifyJob> dj;
   for (const auto& j : jobs) dj.push_back({reinterpret_cast<const void*>(std::get<0>(j)), std::get<1>(j), std::get<2>(j)});
   dev::launch_multi_verify(dj.data(), n, b.scratch, b.out, as_stream(stream));
+}
+
+// ---- checked copy (kernels.hpp CheckedCopyOp) on raw pointers ----
+// (dst, src, bytes, seed, stream_offset, record_index)
+using CheckedOpTuple = std::tuple<uintptr_t, uintptr_t, size_t, uint64_t, uint64_t, int>;
+
+// The distinct record indices of `ops`, ascending; every argument is checked
+// here, before any device work.
+std::vector<int> checked_record_indices(const std::vector<CheckedOpTuple>& ops) {
+  std::vector<int> idx;
+  for (const auto& o : ops) {
+    if (std::get<4>(o) % 4096)
+      throw py::value_error(strfmt("copy_checked: stream_offset %llu is not a multiple of 4096",
+                                   static_cast<unsigned long long>(std::get<4>(o))));
+    if (std::get<5>(o) < 0) throw py::value_error("copy_checked: a record index is >= 0");
+    idx.push_back(std::get<5>(o));
+  }
+  std::sort(idx.begin(), idx.end());
+  idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+  return idx;
+}
+
+// Device records for the current device, grown on demand and never freed
+// (like KernelScratch).  Growing waits for the device: a launch-only caller
+// may still have work in flight on the old ones.
+dev::CopyCheck* checked_records(size_t n) {
+  static dev::CopyCheck* rec = nullptr;
+  static size_t cap = 0;
+  static int device = -1;
+  int dv = 0;
+  if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
+  if (device != dv || n > cap) {
+    if (rec) {
+      (void)hipDeviceSynchronize();
+      (void)hipFree(rec);
+    }
+    cap = std::max<size_t>({n, 2 * cap, 64});
+    if (hipMalloc(&rec, sizeof(dev::CopyCheck) * cap) != hipSuccess) P2P_FATAL("hipMalloc failed");
+    device = dv;
+  }
+  return rec;
+}
+
+std::vector<dev::CheckedCopyOp> checked_ops_arg(const std::vector<CheckedOpTuple>& ops, const std::vector<int>& idx,
+                                                dev::CopyCheck* rec, bool coherent) {
+  std::vector<dev::CheckedCopyOp> v;
+  for (const auto& o : ops) {
+    dev::CheckedCopyOp c;
+    c.src = reinterpret_cast<const void*>(std::get<1>(o));
+    c.dst = reinterpret_cast<void*>(std::get<0>(o));
+    c.bytes = std::get<2>(o);
+    c.coherent = coherent;
+    c.seed = std::get<3>(o);
+    c.stream_offset = std::get<4>(o);
+    c.record = rec + (std::lower_bound(idx.begin(), idx.end(), std::get<5>(o)) - idx.begin());
+    v.push_back(c);
+  }
+  return v;
+}
+
+py::list device_copy_checked(const std::vector<CheckedOpTuple>& ops, uintptr_t stream, bool coherent, int max_blocks,
+                             int accumulate_launches) {
+  if (accumulate_launches < 1) throw py::value_error("copy_checked: accumulate_launches is >= 1");
+  const std::vector<int> idx = checked_record_indices(ops);
+  std::vector<dev::CopyCheck> host(idx.size());
+  if (!idx.empty()) {
+    dev::CopyCheck* rec = checked_records(idx.size());
+    const std::vector<dev::CheckedCopyOp> v = checked_ops_arg(ops, idx, rec, coherent);
+    hipStream_t st = as_stream(stream);
+    py::gil_scoped_release nogil;
+    dev::launch_copy_check_reset(rec, static_cast<int>(idx.size()), st);
+    for (int k = 0; k < accumulate_launches; ++k)
+      dev::launch_multi_copy_checked(v.data(), static_cast<int>(v.size()), st, max_blocks);
+    if (hipMemcpyAsync(host.data(), rec, sizeof(dev::CopyCheck) * idx.size(), hipMemcpyDeviceToHost, st) != hipSuccess)
+      P2P_FATAL("hipMemcpyAsync failed");
+    if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
+  }
+  py::list out;
+  for (const auto& r : host) out.append(py::make_tuple(r.mismatches, r.first_bad));
+  return out;
 }
 
 // ---- mismatch diagnosis (diagnose.hpp) ----
@@ -659,7 +743,7 @@ PYBIND11_MODULE(_p2pcore, m) {
       .def("run", &Session::run, py::arg("mode") = "pair", py::arg("dir") = "uni", py::arg("bytes") = 32u << 20,
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
            py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
-           py::call_guard<NativeCall, py::gil_scoped_release>())
+           py::arg("inline_check") = false, py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("device_latency", &Session::device_latency, py::arg("bytes") = 8, py::arg("iters") = 1000,
@@ -805,6 +889,19 @@ PYBIND11_MODULE(_p2pcore, m) {
       }, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0,
       "The copy kernel over several (dst, src, bytes) ops, as the IPC transport launches a group's receives "
       "(max_blocks > 0: the ops of a launch share that many workgroups and grid-stride).");
+  m.def("copy_checked", &device_copy_checked, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false,
+        py::arg("max_blocks") = 0, py::arg("accumulate_launches") = 1,
+        "The checked copy kernel over [(dst, src, bytes, seed, stream_offset, record_index)]: every word is compared "
+        "with bytes [stream_offset, stream_offset + bytes) of PRNG stream `seed` as it is copied (stream_offset a "
+        "multiple of 4096).  Resets the records, launches accumulate_launches times, reads back once: one "
+        "(mismatching words, first bad stream byte or 2**64-1) per distinct record index, in ascending order.");
+  m.def("copy_checked_launch", [](const std::vector<CheckedOpTuple>& ops, uintptr_t stream, bool coherent, int max_blocks) {
+        const std::vector<int> idx = checked_record_indices(ops);
+        dev::CopyCheck* rec = checked_records(idx.size());
+        const std::vector<dev::CheckedCopyOp> v = checked_ops_arg(ops, idx, rec, coherent);
+        dev::launch_multi_copy_checked(v.data(), static_cast<int>(v.size()), as_stream(stream), max_blocks);
+      }, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0,
+      "Stream-ordered launch of the checked copy only (timing with events): no reset, no readback.");
   m.attr("MAX_SIGNALS") = dev::kMaxSignals;
   m.def("signal", [](const FlagList& posts, const FlagList& waits, uintptr_t status_ptr, uint64_t timeout_ticks,
                      bool release_first, uintptr_t stream, uintptr_t trap_flag) {

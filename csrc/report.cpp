@@ -219,6 +219,16 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
     std::fprintf(out, "  verification: %s (%llu mismatching words; %llu of %llu timed deliveries checked)\n",
                  bad ? "FAILED" : "OK", static_cast<unsigned long long>(bad), static_cast<unsigned long long>(checked),
                  static_cast<unsigned long long>(timed));
+  if (verified && rec.cfg.inline_check) {
+    uint64_t in_flight = 0, in_bad = 0;
+    for (const auto& ph : rec.phases) {
+      in_flight += ph.inline_msgs;
+      in_bad += ph.inline_mismatches;
+    }
+    std::fprintf(out, "  inline check: %s (%llu mismatching words; %llu of %llu timed deliveries checked as they were copied)\n",
+                 in_bad ? "FAILED" : "OK", static_cast<unsigned long long>(in_bad),
+                 static_cast<unsigned long long>(in_flight), static_cast<unsigned long long>(timed));
+  }
   // Phases whose warmup did not verify and were re-posted with smaller ops.
   for (const auto& ph : rec.phases)
     if (!ph.rechunked_to.empty())
@@ -271,6 +281,21 @@ std::string num(double v) {
   if (!std::isfinite(v)) return "null";
   return strfmt("%.6g", v);
 }
+// RunConfig::inline_check: the fields a run and each of its phases gain.
+std::string inline_json(uint64_t msgs, uint64_t bad, uint64_t timed, const std::vector<const PhaseResult*>& phases) {
+  std::string o = strfmt(",\"inline_msgs\":%llu,\"inline_mismatches\":%llu,\"inline_coverage\":%s,\"inline_bad\":[",
+                         static_cast<unsigned long long>(msgs), static_cast<unsigned long long>(bad),
+                         timed ? num(static_cast<double>(msgs) / static_cast<double>(timed)).c_str() : "null");
+  int listed = 0;
+  for (const PhaseResult* ph : phases)
+    for (const InlineBad& b : ph->inline_bad) {
+      if (listed == kMaxInlineBad) break;
+      o += strfmt("%s{\"label\":\"%s\",\"src\":%d,\"dst\":%d,\"iteration\":%d,\"words\":%llu,\"first_bad\":%llu}",
+                  listed++ ? "," : "", json_escape(ph->label).c_str(), b.src, b.dst, b.iteration,
+                  static_cast<unsigned long long>(b.words), static_cast<unsigned long long>(b.first_bad));
+    }
+  return o + "]";
+}
 std::string summary_json(const Summary& s) {
   return strfmt("{\"n\":%zu,\"min\":%s,\"p50\":%s,\"p90\":%s,\"p99\":%s,\"max\":%s,\"mean\":%s}", s.n, num(s.min).c_str(),
                 num(s.p50).c_str(), num(s.p90).c_str(), num(s.p99).c_str(), num(s.max).c_str(), num(s.mean).c_str());
@@ -311,7 +336,18 @@ std::string run_to_json(const RunRecord& rec, int n) {
     << ",\"timing\":\"" << timing_name(rec.cfg.timing) << "\",\"nranks\":" << n << ",\"verify\":"
     << (rec.cfg.verify ? "true" : "false") << ",\"timed_msgs\":" << timed << ",\"verified_msgs\":" << checked
     << ",\"verify_coverage\":" << (rec.cfg.verify && timed ? num(static_cast<double>(checked) / static_cast<double>(timed)) : "null")
-    << ",\"rechunked\":" << (rechunked ? "true" : "false")
+    << ",\"rechunked\":" << (rechunked ? "true" : "false");
+  if (rec.cfg.inline_check) {  // present only when the option is on
+    uint64_t in_flight = 0, in_bad = 0;
+    std::vector<const PhaseResult*> phs;
+    for (const auto& ph : rec.phases) {
+      in_flight += ph.inline_msgs;
+      in_bad += ph.inline_mismatches;
+      phs.push_back(&ph);
+    }
+    o << inline_json(in_flight, in_bad, timed, phs);
+  }
+  o
     << ",\"gbs_matrix\":" << matrix_json(gbs, n) << ",\"p50_us_matrix\":" << matrix_json(flow_matrix_p50_us(rec, n), n)
     << ",\"gbs_min\":" << num(ms.min) << ",\"gbs_mean\":" << num(ms.mean) << ",\"gbs_max\":" << num(ms.max)
     << ",\"phases\":[";
@@ -335,6 +371,7 @@ std::string run_to_json(const RunRecord& rec, int n) {
       o << "}";
     }
     o << "]";
+    if (rec.cfg.inline_check) o << inline_json(ph.inline_msgs, ph.inline_mismatches, ph.timed_msgs, {&ph});
     // RunConfig::diagnose: present only when something was found.
     if (!ph.diagnosis.empty()) {
       o << ",\"diagnosis\":[";

@@ -135,7 +135,8 @@ std::vector<Transport::GroupFlow> group_flow_list(const Phase& phase) {
 
 }  // namespace
 
-void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen) {
+void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen,
+                          const InlineRecords* check) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const std::vector<int> rs = remote_slots(phase, t.rank());
   const int base = gen * std::max(1, phase.max_recv_slots());
@@ -150,8 +151,13 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
     t.group_flows(bufs.send_buf(), flows, bytes);
   }
   for (size_t j = 0; j < ops.send_to.size(); ++j) t.send_to_slot(bufs.send_at(off), bytes, ops.send_to[j], base + rs[j]);
-  for (size_t i = 0; i < ops.recv_from.size(); ++i)
-    t.recv_from(bufs.recv_buf(base + static_cast<int>(i)), bytes, ops.recv_from[i], off);
+  for (size_t i = 0; i < ops.recv_from.size(); ++i) {
+    if (check)
+      t.recv_checked(bufs.recv_buf(base + static_cast<int>(i)), bytes, ops.recv_from[i], off,
+                     generation_seed(ops.recv_from[i], bytes, check->salt, gen), check->first + i);
+    else
+      t.recv_from(bufs.recv_buf(base + static_cast<int>(i)), bytes, ops.recv_from[i], off);
+  }
   t.group_end();
 }
 
@@ -262,6 +268,11 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
 //             generation 1's stream of the same sender: a whole delivery that
 //             is a valid payload, only not the one due (the diagnosis must name
 //             it, RunConfig::diagnose), exit 2,
+//   corrupt-send — after the warmup and its check, before the timed loop, the
+//             rank zeroes the first 64 B of its generation-0 send region: every
+//             timed delivery from that region is wrong at the source.  The
+//             check after timing sees the one slot that kept such a delivery;
+//             the inline check (RunConfig::inline_check) sees each of them,
 //   exit    — the rank dies abruptly (peers must fail, not hang),
 //   hang    — the rank stops responding (peers' watchdogs must fire).
 struct FaultSpec {
@@ -304,7 +315,7 @@ namespace {
 void maybe_inject_fault(Transport& t, Buffers& bufs, int rank, size_t phase_index, size_t bytes, const Phase& phase,
                         uint64_t salt, int gens) {
   const FaultSpec& f = fault_spec();
-  if (f.kind.empty() || f.kind == "skip" || f.kind == "skip-some" || f.rank != rank) return;
+  if (f.kind.empty() || f.kind == "skip" || f.kind == "skip-some" || f.kind == "corrupt-send" || f.rank != rank) return;
   if (f.phase >= 0 && static_cast<size_t>(f.phase) != phase_index) return;
   if (f.kind == "corrupt") {
     if (bufs.slots() > 0) {
@@ -576,6 +587,23 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
       t.sync();
     }
   }
+  if (active && fault_applies("corrupt-send", me, static_cast<long>(phase_index)) &&
+      !phase.ranks[static_cast<size_t>(me)].send_to.empty()) {
+    std::fprintf(stderr, "[p2p] injected fault: rank %d zeroes the first bytes of its generation-0 send region\n", me);
+    t.zero(bufs.send_at(0), std::min<size_t>(cfg.bytes, 64));
+    t.sync();
+  }
+  // Inline check: a record per timed delivery on this rank (iteration-major),
+  // made and reset after the warmup's own check and before the timed barrier.
+  const size_t nrecv = active ? phase.ranks[static_cast<size_t>(me)].recv_from.size() : 0;
+  const bool inline_on = cfg.verify && cfg.inline_check;
+  if (inline_on) {
+    P2P_CHECK(t.supports_inline_check(), "inline check: this transport cannot check a delivery as it is copied");
+    if (nrecv) {
+      t.inline_check_begin(nrecv * static_cast<size_t>(cfg.iters));
+      t.sync();
+    }
+  }
   const bool skip = active && fault_applies("skip", me, static_cast<long>(phase_index));
   const bool skip_some = active && fault_applies("skip-some", me, static_cast<long>(phase_index));
   if (skip) {
@@ -587,7 +615,8 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   // Iteration i posts generation i mod gens; skip-some drops the even ones.
   auto post = [&](int i) {
     if (skip_some) t.set_discard(i % 2 == 0);
-    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens);
+    const InlineRecords rec{static_cast<size_t>(i) * nrecv, cfg.salt};
+    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr);
   };
 
   double my_seconds = 0;
@@ -645,6 +674,29 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   res.wall_seconds = w1 - w0;
   if (skip || skip_some) t.set_discard(false);
 
+  // The inline records, read once after the timed sync and before the check
+  // of the slots: wrong words per receive slot, and this rank's first wrong
+  // deliveries as text (one "I" line each, parsed back on every rank).
+  const int maxslots = std::max(1, phase.max_recv_slots());
+  std::vector<uint64_t> inline_slot(static_cast<size_t>(maxslots), 0);
+  uint64_t inline_cover = 0;
+  std::string inline_text;
+  if (inline_on && nrecv) {
+    const std::vector<Transport::InlineCheck> recs = t.inline_check_results();
+    const RankOps& ops = phase.ranks[static_cast<size_t>(me)];
+    int listed = 0;
+    for (size_t k = 0; k < recs.size(); ++k) {
+      if (!recs[k].mismatches) continue;
+      const size_t i = k % nrecv;
+      inline_slot[i] += recs[k].mismatches;
+      if (listed++ < kMaxInlineBad)
+        inline_text += strfmt("I %d %d %zu %llu %llu\n", ops.recv_from[i], me, k / nrecv,
+                              static_cast<unsigned long long>(recs[k].mismatches),
+                              static_cast<unsigned long long>(recs[k].first_bad));
+    }
+    inline_cover = recs.size();
+  }
+
   if (active) maybe_inject_fault(t, bufs, me, phase_index, cfg.bytes, phase, cfg.salt, gens);
 
   std::string err = t.async_error();
@@ -653,13 +705,11 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   // Verification of every receive slot of every generation on this rank:
   // per slot, the wrong words summed over generations and generation 0's
   // checksum.
-  const int maxslots = std::max(1, phase.max_recv_slots());
   std::vector<uint64_t> vr(static_cast<size_t>(maxslots) * 2, 0);
   const int timed_gens = std::min(gens, cfg.iters);
   uint64_t cover[2] = {0, 0};  // timed deliveries, verified deliveries (this rank)
   std::vector<uint64_t> job_bad;  // wrong words per (generation, slot) of this rank
   if (active) {
-    const uint64_t nrecv = phase.ranks[static_cast<size_t>(me)].recv_from.size();
     cover[0] = nrecv * static_cast<uint64_t>(cfg.iters);
     if (cfg.verify) {
       check_slots(t, phase, cfg, bufs, timed_gens, &vr, &job_bad);
@@ -668,6 +718,33 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   }
   res.timed_msgs = boot.allreduce_sum_u64(cover[0]);
   res.verified_msgs = boot.allreduce_sum_u64(cover[1]);
+  // Collective whenever it is on, like the diagnosis below.
+  std::vector<uint64_t> all_inline;
+  if (inline_on) {
+    res.inline_msgs = boot.allreduce_sum_u64(inline_cover);
+    all_inline = boot.allgather_vector(inline_slot);
+    for (const std::string& s : boot.allgather_string(inline_text)) {
+      size_t at = 0;
+      while (at < s.size() && res.inline_bad.size() < static_cast<size_t>(kMaxInlineBad)) {
+        size_t nl = s.find('\n', at);
+        if (nl == std::string::npos) nl = s.size();
+        InlineBad b;
+        unsigned long long words = 0, first = 0;
+        P2P_CHECK(std::sscanf(s.substr(at, nl - at).c_str(), "I %d %d %d %llu %llu", &b.src, &b.dst, &b.iteration, &words,
+                              &first) == 5,
+                  "malformed inline check record");
+        b.words = words;
+        b.first_bad = first;
+        res.inline_bad.push_back(b);
+        at = nl + 1;
+      }
+    }
+    if (me == 0)
+      for (const InlineBad& b : res.inline_bad)
+        std::fprintf(stderr, "[p2p] inline check %s %d->%d iteration %d: %llu wrong words, first at byte %llu\n",
+                     phase.label.c_str(), b.src, b.dst, b.iteration, static_cast<unsigned long long>(b.words),
+                     static_cast<unsigned long long>(b.first_bad));
+  }
   // Collective whenever it is on: a rank without wrong words sends nothing.
   if (cfg.verify && cfg.diagnose > 0) {
     const std::string mine = diagnose_slots(t, phase, cfg, bufs, gens, res.op_bytes, job_bad);
@@ -711,6 +788,11 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
       fr.verified = true;
       fr.mismatches = all_vr[base];
       fr.checksum = all_vr[base + 1];
+      if (inline_on) {
+        const uint64_t in_flight = all_inline[static_cast<size_t>(f.dst) * inline_slot.size() + static_cast<size_t>(slots[fi])];
+        fr.mismatches += in_flight;
+        res.inline_mismatches += in_flight;
+      }
       res.total_mismatches += fr.mismatches;
     }
     res.flows.push_back(fr);

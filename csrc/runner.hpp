@@ -39,7 +39,7 @@ struct RunConfig {
   int warmup = 8;            // reference: none (p2p_matrix.cc:153-172)
   Timing timing = Timing::Events;
   // Random-filled sends, every received buffer checked on the device after
-  // the timed loop (never inside it).  On by default: the
+  // the timed loop (never inside it; inline_check below adds a check that is).  On by default: the
   // reference's zeroed buffers are never read back (p2p_matrix.cc:129-130),
   // so a transfer that silently drops bytes would print as a fast cell.
   // p2p_matrix --no-verify opts out.
@@ -61,6 +61,23 @@ struct RunConfig {
   // diagnoses its first `diagnose` failing (generation, slot) pairs
   // (Transport::diagnose; PhaseResult::diagnosis).  0: off, nothing changes.
   int diagnose = 0;
+  // With verify, on a transport with Transport::supports_inline_check (the
+  // IPC pull engine): every timed delivery is also compared with its stream
+  // as the copy kernel moves it, inside the timed loop, one record each --
+  // coverage 1.0 at any size and iteration count, whatever `gens` the memory
+  // allows.  It tests what the receiver loaded, not that the store landed:
+  // the check of the slots after timing runs as always.  Warm-up iterations
+  // are posted unchecked.  Off: nothing changes.
+  bool inline_check = false;
+};
+
+// One timed delivery the inline check found wrong (RunConfig::inline_check).
+constexpr int kMaxInlineBad = 8;
+struct InlineBad {
+  int src = -1, dst = -1;
+  int iteration = 0;       // timed iteration, from 0
+  uint64_t words = 0;      // wrong 32-bit words
+  uint64_t first_bad = 0;  // byte offset of the first one in the message
 };
 
 // What the diagnosis found in one receive slot of one generation: at most
@@ -108,6 +125,12 @@ struct PhaseResult {
   int generations = 1;
   uint64_t timed_msgs = 0;
   uint64_t verified_msgs = 0;
+  // RunConfig::inline_check (all ranks): deliveries checked in flight, their
+  // wrong words (also in FlowResult::mismatches and total_mismatches), and
+  // the first kMaxInlineBad wrong deliveries in rank, then iteration order.
+  uint64_t inline_msgs = 0;
+  uint64_t inline_mismatches = 0;
+  std::vector<InlineBad> inline_bad;
   // Op size the phase's messages were posted as (largest over this rank's
   // peers; 0 = one op per message) and what the warmup check saw: wrong words
   // in the first warmup and the op sizes it had to fall back to.
@@ -163,8 +186,15 @@ std::vector<int> remote_slots(const Phase& phase, int me);
 
 // Posts one iteration (one group) of `phase` for this rank, generation `gen`:
 // the payload comes from send region gen (slot_stride(bytes) apart) and lands
-// in receive slots gen * phase.max_recv_slots() + i.
-void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0);
+// in receive slots gen * phase.max_recv_slots() + i.  With `check` (its
+// first record, `salt`), receive i is posted as Transport::recv_checked
+// against generation_seed(sender, bytes, salt, gen) into record first + i.
+struct InlineRecords {
+  size_t first = 0;
+  uint64_t salt = 0;
+};
+void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0,
+                          const InlineRecords* check = nullptr);
 
 // Receive generations for verified runs of messages up to `max_bytes` with
 // `slots` receive slots per iteration and up to `iters` iterations: as many as

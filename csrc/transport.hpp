@@ -91,6 +91,30 @@ class Transport {
   // buffer set (the receiver's index of this sender in its recv list).  Push
   // transports need it to address the peer's memory; the rest ignore it.
   virtual void send_to_slot(const void* p, size_t bytes, int peer, int /*remote_slot*/) { send(p, bytes, peer); }
+  // ---- inline check: every delivery compared as it is copied ----
+  // A transport whose own kernel moves the payload (the IPC pull engine) can
+  // regenerate the word it expects while the loaded one sits in a register,
+  // so a delivery is checked inside the timed loop at no cost in memory.  It
+  // tests what the receiver LOADED (the same value it then stores), not that
+  // the store landed: the check of the slots after timing stays.
+  //   inline_check_begin(n)  n records, reset to {0, ~0}, stream-ordered;
+  //   recv_checked(...)      recv_from whose data is the first `bytes` of
+  //                          stream `seed`, its findings added to record
+  //                          `record_index` (a discarded receive adds none);
+  //   inline_check_results() blocking, one readback: one entry per record.
+  // Not inside a graph capture: the record would be baked into the graph.
+  struct InlineCheck {
+    uint64_t mismatches = 0;     // wrong 32-bit words (a partial tail word counts once)
+    uint64_t first_bad = ~0ull;  // lowest wrong byte offset of the message, ~0 if none
+  };
+  virtual bool supports_inline_check() const { return false; }
+  virtual void inline_check_begin(size_t /*nrecords*/) {}
+  virtual void recv_checked(void* p, size_t bytes, int peer, size_t src_offset, uint64_t /*seed*/,
+                            size_t /*record_index*/) {
+    recv_from(p, bytes, peer, src_offset);
+  }
+  virtual std::vector<InlineCheck> inline_check_results() { return {}; }
+
   // Multi-path transports (IPC relay engine) move parts of a message through
   // ranks that are neither its sender nor its receiver, so every rank must
   // know every flow of a group.  When wants_group_flows() is true the runner

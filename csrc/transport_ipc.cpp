@@ -130,6 +130,8 @@ class IpcTransport final : public Transport {
     for (auto ev : events_) (void)hipEventDestroy(ev);
     if (acc_) (void)hipFree(acc_);
     if (acc_host_) (void)hipHostFree(acc_host_);
+    if (check_dev_) (void)hipFree(check_dev_);
+    if (check_host_) (void)hipHostFree(check_host_);
     if (stream_) (void)hipStreamDestroy(stream_);
   }
 
@@ -300,6 +302,7 @@ class IpcTransport final : public Transport {
     P2P_CHECK(!in_group_, "nested group");
     in_group_ = true;
     ops_.clear();
+    checked_ops_.clear();
     covered_.clear();
   }
 
@@ -361,6 +364,52 @@ class IpcTransport final : public Transport {
   }
   void recv(void* p, size_t bytes, int peer) override { recv_from(p, bytes, peer, 0); }
   void recv_from(void* p, size_t bytes, int peer, size_t src_offset) override {
+    post_recv(p, bytes, peer, src_offset, nullptr, 0);
+  }
+
+  // ---- inline check (transport.hpp): the pull engine's own kernel compares
+  // each word it loads with the stream the sender filled (kernels.hpp
+  // multi_copy_checked_kernel); one device record per delivery.
+  bool supports_inline_check() const override { return engine_ == "kernel"; }
+  // The records and their pinned mirror grow on demand; the stream may still
+  // write the old ones, so it is drained first (bounded, abort-aware sync()),
+  // as BatchVerifier::reserve does.
+  void inline_check_begin(size_t nrecords) override {
+    P2P_CHECK(supports_inline_check(), "ipc transport: the inline check needs --ipc-engine kernel");
+    if (nrecords > check_cap_) {
+      if (check_dev_ || check_host_) sync();
+      if (check_dev_) HIPCHECK(hipFree(check_dev_));
+      if (check_host_) HIPCHECK(hipHostFree(check_host_));
+      check_dev_ = check_host_ = nullptr;
+      check_cap_ = std::max(nrecords, 2 * check_cap_);
+      HIPCHECK(hipMalloc(&check_dev_, sizeof(dev::CopyCheck) * check_cap_));
+      HIPCHECK(hipHostMalloc(&check_host_, sizeof(dev::CopyCheck) * check_cap_, hipHostMallocDefault));
+    }
+    check_n_ = nrecords;
+    dev::launch_copy_check_reset(check_dev_, static_cast<int>(nrecords), stream_);
+  }
+  void recv_checked(void* p, size_t bytes, int peer, size_t src_offset, uint64_t seed, size_t record_index) override {
+    P2P_CHECK(supports_inline_check(), "ipc transport: the inline check needs --ipc-engine kernel");
+    // A replayed graph would write the record it captured, whatever it delivers.
+    P2P_CHECK(!capturing_, "ipc transport: no inline check inside a graph capture");
+    P2P_CHECK(record_index < check_n_, "ipc transport: inline_check_begin() first, with enough records");
+    post_recv(p, bytes, peer, src_offset, &seed, record_index);
+  }
+  std::vector<InlineCheck> inline_check_results() override {
+    std::vector<InlineCheck> out(check_n_);
+    if (!check_n_) return out;
+    HIPCHECK(hipMemcpyAsync(check_host_, check_dev_, sizeof(dev::CopyCheck) * check_n_, hipMemcpyDeviceToHost, stream_));
+    sync();
+    for (size_t i = 0; i < check_n_; ++i) {
+      out[i].mismatches = check_host_[i].mismatches;
+      out[i].first_bad = check_host_[i].first_bad;
+    }
+    return out;
+  }
+
+  // A receive; with `seed`, one the kernel checks against that stream into
+  // record `record_index`.
+  void post_recv(void* p, size_t bytes, int peer, size_t src_offset, const uint64_t* seed, size_t record_index) {
     P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
     const Registration* reg = nullptr;
     int slot = -1;
@@ -379,10 +428,21 @@ class IpcTransport final : public Transport {
       return;
     }
     P2P_CHECK(src_offset + bytes <= reg->send_bytes, "ipc transport: receive beyond the peer's send buffer");
-    // Injected skip fault: the pull is not issued.
-    if (!discarding())
-      ops_.push_back({static_cast<const char*>(reg->peer_send[static_cast<size_t>(peer)]) + src_offset, p, bytes,
-                      peer != rank_});
+    // Injected skip fault: the pull is not issued (and a checked one leaves
+    // its record at 0 wrong words: the check after timing catches it).
+    if (!discarding()) {
+      const dev::CopyOp op{static_cast<const char*>(reg->peer_send[static_cast<size_t>(peer)]) + src_offset, p, bytes,
+                           peer != rank_};
+      if (seed) {
+        dev::CheckedCopyOp c;
+        static_cast<dev::CopyOp&>(c) = op;
+        c.seed = *seed;
+        c.record = check_dev_ + record_index;
+        checked_ops_.push_back(c);
+      } else {
+        ops_.push_back(op);
+      }
+    }
     if (!in_group_) flush();
   }
   void group_end() override {
@@ -411,8 +471,12 @@ class IpcTransport final : public Transport {
   // Push / relay: the flag values are baked into each launch, so a replay
   // would wait for flags that were already consumed; no graphs there.
   bool supports_graphs() const override { return engine_ == "kernel"; }
-  void capture_begin() override { HIPCHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal)); }
+  void capture_begin() override {
+    HIPCHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+    capturing_ = true;
+  }
   int capture_end() override {
+    capturing_ = false;
     hipGraph_t g = nullptr;
     HIPCHECK(hipStreamEndCapture(stream_, &g));
     hipGraphExec_t ex = nullptr;
@@ -796,6 +860,13 @@ class IpcTransport final : public Transport {
       flush_push();
       return;
     }
+    // Kernel engine: the checked kernel when the group has checked receives
+    // (the runner posts a group either all checked or all plain; plain ones
+    // next to them go in the plain kernel), the plain kernel otherwise.
+    if (!checked_ops_.empty()) {
+      dev::launch_multi_copy_checked(checked_ops_.data(), static_cast<int>(checked_ops_.size()), stream_);
+      checked_ops_.clear();
+    }
     if (ops_.empty()) return;
     if (engine_ == "kernel") {
       dev::launch_multi_copy(ops_.data(), static_cast<int>(ops_.size()), stream_);
@@ -867,6 +938,11 @@ class IpcTransport final : public Transport {
   std::vector<Registration> regs_;
   bool in_group_ = false;
   std::vector<dev::CopyOp> ops_;
+  std::vector<dev::CheckedCopyOp> checked_ops_;  // kernel engine: receives checked as they are copied
+  dev::CopyCheck* check_dev_ = nullptr;          // one record per checked delivery (inline_check_begin)
+  dev::CopyCheck* check_host_ = nullptr;         // pinned mirror, one readback
+  size_t check_cap_ = 0, check_n_ = 0;
+  bool capturing_ = false;
   std::vector<std::array<int, 3>> covered_;  // relay: (src, dst, slot) posted by group_flows
   unsigned long long relayed_bytes_ = 0, relayed_stripes_ = 0;  // moved by this rank as a relay (P2P_RELAY_STATS)
   bool debug_ = std::getenv("P2P_IPC_DEBUG") != nullptr;     // per-group flag bookkeeping on stderr

@@ -143,6 +143,56 @@ def reference_verify(data: torch.Tensor, seed: int) -> VerifyResult:
     return VerifyResult(int(bad.numel()), csum, first)
 
 
+# ------------------------------------------------------------- checked copy --
+
+class CopyCheck(NamedTuple):
+    """What the checked copy found in one op (csrc/kernels.hpp CopyCheck)."""
+    mismatches: int   # mismatching 32-bit words (tail: partial word counts once)
+    first_bad: int    # lowest mismatching stream byte (stream_offset + position), 2**64-1 if none
+
+    @property
+    def ok(self) -> bool:
+        return self.mismatches == 0
+
+
+def copy_checked_(dst: torch.Tensor, src: torch.Tensor, seed: int, *, stream_offset: int = 0, coherent: bool = False,
+                  max_blocks: int = 0, stream: Optional[torch.cuda.Stream] = None) -> CopyCheck:
+    """Copies ``src`` into ``dst`` with the gfx950 checked copy kernel, which
+    compares every word it loads with bytes ``[stream_offset, stream_offset +
+    nbytes)`` of PRNG stream ``seed`` on its way through (blocking).  ``dst``
+    receives what was loaded whether or not it matched.  ``stream_offset`` is
+    a multiple of 4096; ``coherent`` selects the cross-GPU access form."""
+    nbytes = _check_tensor(src)
+    if _check_tensor(dst) != nbytes:
+        raise ValueError("copy_checked_: dst and src differ in size")
+    r = require_native().copy_checked([(dst.data_ptr(), src.data_ptr(), nbytes, seed & (2**64 - 1), stream_offset, 0)],
+                                      _stream(stream), coherent, max_blocks)
+    return CopyCheck(*r[0])
+
+
+def reference_copy_check(src: torch.Tensor, seed: int, stream_offset: int = 0) -> CopyCheck:
+    """PyTorch implementation of the checked copy's contract on a uint8
+    tensor holding stream bytes from ``stream_offset`` (a multiple of 4) on:
+    wrong 32-bit words, the final partial word masked, and the first wrong
+    stream byte.  Built on :func:`reference_words`."""
+    assert stream_offset % 4 == 0
+    data = src.reshape(-1).to(torch.uint8)
+    nbytes = data.numel()
+    nwords = (nbytes + 3) // 4
+    if not nwords:
+        return CopyCheck(0, 2**64 - 1)
+    pad = nwords * 4 - nbytes
+    d = torch.cat([data, torch.zeros(pad, dtype=torch.uint8, device=data.device)]).to(torch.int64).reshape(nwords, 4)
+    mask = torch.full((nwords,), M32, dtype=torch.int64, device=data.device)
+    if pad:
+        mask[-1] = (1 << (8 * (4 - pad))) - 1
+    got = (d[:, 0] | (d[:, 1] << 8) | (d[:, 2] << 16) | (d[:, 3] << 24)) & mask
+    want = reference_words(stream_offset // 4, nwords, seed, data.device) & mask
+    bad = (got != want).nonzero().reshape(-1)
+    first = stream_offset + int(bad[0].item()) * 4 if bad.numel() else 2**64 - 1
+    return CopyCheck(int(bad.numel()), first)
+
+
 # ---------------------------------------------------------------- diagnosis --
 
 class GranuleRecord(NamedTuple):
