@@ -176,6 +176,12 @@ class Session {
     t_->group_end();
   }
 
+  // Test hooks for the timing tests: the transport's own marks, so a test can
+  // bracket work it posted itself.  elapsed_ms is valid after a sync.
+  int mark() { return t_->mark(); }
+  double elapsed_ms(int from, int to) { return t_->elapsed_ms(from, to); }
+  void clear_marks() { t_->clear_marks(); }
+
   // Test hook for the stream gate: arm one, release it or not, wait for the
   // stream.  An unreleased gate must open by itself at its deadline.
   std::string gate_probe(double timeout_s, bool release) {
@@ -775,7 +781,14 @@ PYBIND11_MODULE(_p2pcore, m) {
            py::call_guard<NativeCall, py::gil_scoped_release>(),
            "Test hook: a receive no send matches, left pending; the session's teardown must still end.")
       .def("_unmatched_recv", &Session::unmatched_recv, py::arg("bytes") = size_t{1} << 20,
-           py::call_guard<NativeCall, py::gil_scoped_release>(), "Test hook: a receive no send matches; returns the watchdog's error.");
+           py::call_guard<NativeCall, py::gil_scoped_release>(), "Test hook: a receive no send matches; returns the watchdog's error.")
+      .def("_mark", &Session::mark, py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: a timestamp of the transport behind all work posted so far; returns its id.")
+      .def("_elapsed_ms", &Session::elapsed_ms, py::arg("a"), py::arg("b"),
+           py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: milliseconds between two marks of the transport; valid after a sync.")
+      .def("_clear_marks", &Session::clear_marks, py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: forget the transport's marks (their ids are handed out again).");
 
   py::class_<PyStepDriver>(m, "StepDriver")
       .def(py::init<std::shared_ptr<Session>, const std::string&, const std::string&, size_t, int, bool, bool, bool, int,

@@ -872,6 +872,515 @@ TEST(test_step_driver_split_groups) {
     }, mode == 1);
 }
 
+// ------------------------------------ reported times on a scripted clock ----
+//
+// The engine's arithmetic on marks (run_phase, run_latency, StepDriver) with
+// a transport that moves the data through the host transport but owns time:
+// mark() returns the ordinal j of the mark since the last clear_marks(), and
+// rank r's mark j lies at T_r(j) = sum_{i<j} d_r(i) milliseconds with
+// d_r(i) = (r + 1) * (1 + (5 i mod 7)) / 64.  Every value and partial sum is
+// exact in a double; the steps are irregular, so a mark paired with the wrong
+// neighbour shows; ranks differ, so the slower endpoint is decidable.  The
+// expected values below come from T_r by plain loops (summarize, which has
+// its own test, is applied to the expected sample list).
+
+static double script_step_ms(int r, long i) { return (r + 1) * static_cast<double>(1 + (5 * i) % 7) / 64.0; }
+static double script_T(int r, long j) {
+  double t = 0;
+  for (long i = 0; i < j; ++i) t += script_step_ms(r, i);
+  return t;
+}
+
+class ScriptedClock final : public Transport {
+ public:
+  explicit ScriptedClock(Transport& t, int concurrency = 1, bool relay = false) : t_(&t), k_(concurrency), relay_(relay) {}
+  std::string name() const override { return "scripted-clock"; }
+  int rank() const override { return t_->rank(); }
+  int nranks() const override { return t_->nranks(); }
+  void* alloc(size_t b) override { return t_->alloc(b); }
+  void release(void* p) override { t_->release(p); }
+  void fill(void* p, size_t b, uint64_t s) override { t_->fill(p, b, s); }
+  void zero(void* p, size_t b) override { t_->zero(p, b); }
+  VerifyResult verify(const void* p, size_t b, uint64_t s) override { return t_->verify(p, b, s); }
+  void group_begin() override { t_->group_begin(); }
+  void send(const void* p, size_t b, int peer) override { t_->send(p, b, peer); }
+  void recv(void* p, size_t b, int peer) override { t_->recv(p, b, peer); }
+  void group_end() override {
+    t_->group_end();
+    log += 'g';
+  }
+  bool gate_arm(double s) override { return t_->gate_arm(s); }
+  void gate_release() override { t_->gate_release(); }
+  bool gate_timed_out() override { return t_->gate_timed_out(); }
+  bool wants_group_flows() const override { return relay_; }
+  int mark() override {
+    log += 'm';
+    return next_++;
+  }
+  double elapsed_ms(int a, int b) override {
+    asked.emplace_back(a, b);
+    return script_T(rank(), b) - script_T(rank(), a);
+  }
+  void clear_marks() override {
+    log += 'c';
+    next_ = 0;
+  }
+  int concurrency() const override { return k_; }
+  void sync() override {
+    t_->sync();
+    log += 's';
+  }
+  long count(char what) const { return std::count(log.begin(), log.end(), what); }
+
+  std::string log;                         // c(lear) m(ark) g(roup_end) s(ync), in order
+  std::vector<std::pair<int, int>> asked;  // every elapsed_ms(a, b), in order
+
+ private:
+  Transport* t_;
+  int k_;
+  bool relay_;  // asks for every group's flows: ranks outside a phase post and time it too
+  int next_ = 0;
+};
+
+static bool rel_eq(double a, double b) { return std::fabs(a - b) <= 1e-12 * std::max(std::fabs(a), std::fabs(b)); }
+#define EXPECT_REL(a, b) EXPECT(rel_eq((a), (b)))
+
+static void expect_summary(const Summary& got, const std::vector<double>& want_samples) {
+  const Summary w = summarize(want_samples);
+  EXPECT(got.n == w.n);
+  EXPECT_REL(got.min, w.min);
+  EXPECT_REL(got.max, w.max);
+  EXPECT_REL(got.mean, w.mean);
+  EXPECT_REL(got.stdev, w.stdev);
+  EXPECT_REL(got.p50, w.p50);
+  EXPECT_REL(got.p90, w.p90);
+  EXPECT_REL(got.p99, w.p99);
+}
+
+static std::string repeat(const std::string& s, int n) {
+  std::string o;
+  for (int i = 0; i < n; ++i) o += s;
+  return o;
+}
+
+struct ScriptedRun {
+  PhaseResult res;
+  std::string log;
+  std::vector<std::pair<int, int>> asked;
+};
+
+// One phase on n ranks over the scripted clock; what every rank got.
+static std::vector<ScriptedRun> scripted_phase(int n, const Phase& phase, const RunConfig& cfg, int concurrency = 1,
+                                               bool relay = false) {
+  std::vector<ScriptedRun> out(static_cast<size_t>(n));
+  run_ranks(n, [&](Bootstrap& b, Transport& host) {
+    ScriptedClock t(host, concurrency, relay);
+    Buffers bufs(t, cfg.bytes, std::max(1, phase.max_recv_slots()));
+    ScriptedRun& r = out[static_cast<size_t>(b.rank())];
+    r.res = run_phase(t, b, phase, 0, cfg, bufs);
+    r.log = t.log;
+    r.asked = t.asked;
+    b.barrier();
+  });
+  return out;
+}
+
+static RunConfig scripted_config(int iters, int warmup) {
+  RunConfig cfg;
+  cfg.bytes = 4100;
+  cfg.iters = iters;
+  cfg.warmup = warmup;
+  cfg.verify = true;
+  return cfg;
+}
+
+// The numbers of an events-timed phase that follow from each rank's scripted
+// time `T_r(last)` over its timed window: rank_seconds, the flows' seconds and
+// rates, the phase's seconds and rates.
+static void expect_phase_numbers(const PhaseResult& res, const Phase& phase, const RunConfig& cfg, long last) {
+  const int n = static_cast<int>(phase.ranks.size());
+  const double iters = cfg.iters;
+  EXPECT(res.rank_seconds.size() == static_cast<size_t>(n));
+  double slowest = 0;
+  for (int r = 0; r < n; ++r) {
+    const double want = phase.participates(r) ? script_T(r, last) / 1e3 : 0.0;
+    EXPECT_REL(res.rank_seconds[static_cast<size_t>(r)], want);
+    slowest = std::max(slowest, want);
+  }
+  EXPECT(slowest > 0);
+  EXPECT_REL(res.seconds_per_iter, slowest / iters);
+  const double bytes = static_cast<double>(cfg.bytes);
+  EXPECT(res.bytes_per_iter == bytes * static_cast<double>(phase.flows.size()));
+  EXPECT_REL(res.agg_gbs, bytes * static_cast<double>(phase.flows.size()) / (slowest / iters) / 1e9);
+  EXPECT(res.flows.size() == phase.flows.size());
+  for (size_t i = 0; i < res.flows.size() && i < phase.flows.size(); ++i) {
+    const FlowResult& f = res.flows[i];
+    EXPECT(f.flow == phase.flows[i]);
+    const double s = std::max(script_T(f.flow.src, last), script_T(f.flow.dst, last)) / 1e3 / iters;
+    EXPECT_REL(f.seconds, s);
+    EXPECT_REL(f.gbs, bytes / s / 1e9);
+    EXPECT_REL(f.gbps, 8.0 * bytes / s / 1e9);
+    EXPECT(f.verified && f.mismatches == 0);
+  }
+}
+
+TEST(test_scripted_run_phase_events) {
+  const int n = 4, iters = 10, warmup = 3;
+  const Phase phase = make_tournament_schedule(n, Direction::Bi).phases[0];
+  EXPECT(phase.flows.size() == 4);
+  const RunConfig cfg = scripted_config(iters, warmup);
+  const auto runs = scripted_phase(n, phase, cfg);
+  for (int me = 0; me < n; ++me) {
+    const ScriptedRun& run = runs[static_cast<size_t>(me)];
+    // One mark before the first timed group and one after each; the warmup's
+    // groups lie before the clear and carry no mark.
+    const size_t clear = run.log.rfind('c');
+    EXPECT(clear != std::string::npos);
+    if (clear == std::string::npos) continue;
+    EXPECT(run.log.substr(clear + 1) == "m" + repeat("gm", iters) + "s");
+    const std::string before = run.log.substr(0, clear);
+    EXPECT(std::count(before.begin(), before.end(), 'g') == warmup);
+    EXPECT(before.find('m') == std::string::npos && before.find('c') == std::string::npos);
+    EXPECT(!before.empty() && before.back() == 's');  // the warmup was waited for before the window opened
+
+    expect_phase_numbers(run.res, phase, cfg, iters);
+    // The pair without rank 3 is not charged rank 3's time.
+    int without3 = 0;
+    for (const FlowResult& f : run.res.flows) {
+      if (f.flow.src == 3 || f.flow.dst == 3) continue;
+      ++without3;
+      EXPECT(f.seconds < script_T(3, iters) / 1e3 / iters);
+      EXPECT_REL(f.seconds, script_T(std::max(f.flow.src, f.flow.dst), iters) / 1e3 / iters);
+    }
+    EXPECT(without3 == 2);
+    EXPECT_REL(run.res.seconds_per_iter, script_T(3, iters) / 1e3 / iters);
+    // iter_us of a -> b: the receiver's mark-to-mark intervals.
+    for (const FlowResult& f : run.res.flows) {
+      std::vector<double> want;
+      for (long i = 0; i < iters; ++i) want.push_back((script_T(f.flow.dst, i + 1) - script_T(f.flow.dst, i)) * 1e3);
+      expect_summary(f.iter_us, want);
+    }
+  }
+}
+
+TEST(test_scripted_run_phase_concurrency_and_no_samples) {
+  const int n = 4, k = 4;
+  const Phase phase = make_tournament_schedule(n, Direction::Bi).phases[0];
+  // K messages in flight: a sample spans K marks and is divided by K; the
+  // marks left over after the last full round go into none; fewer than K
+  // marks give one averaged sample.
+  for (int iters : {10, 3, 8}) {
+    const RunConfig cfg = scripted_config(iters, 1);
+    const auto runs = scripted_phase(n, phase, cfg, k);
+    for (int me = 0; me < n; ++me) {
+      const ScriptedRun& run = runs[static_cast<size_t>(me)];
+      expect_phase_numbers(run.res, phase, cfg, iters);  // the window does not depend on the grouping
+      for (const FlowResult& f : run.res.flows) {
+        const int d = f.flow.dst;
+        std::vector<double> want;
+        if (iters == 10)
+          want = {(script_T(d, 4) - script_T(d, 0)) * 1e3 / 4, (script_T(d, 8) - script_T(d, 4)) * 1e3 / 4};
+        else if (iters == 3)
+          want = {script_T(d, 3) * 1e3 / 3};
+        else
+          want = {(script_T(d, 4) - script_T(d, 0)) * 1e3 / 4, (script_T(d, 8) - script_T(d, 4)) * 1e3 / 4};
+        expect_summary(f.iter_us, want);
+        if (iters == 8)  // two samples that tile the window
+          EXPECT_REL(f.iter_us.mean * 2 * 4, script_T(d, 8) * 1e3);
+      }
+    }
+  }
+  // samples off: a mark before the first group and one after the last.
+  RunConfig cfg = scripted_config(10, 3);
+  cfg.samples = false;
+  const auto runs = scripted_phase(n, phase, cfg);
+  for (int me = 0; me < n; ++me) {
+    const ScriptedRun& run = runs[static_cast<size_t>(me)];
+    const size_t clear = run.log.rfind('c');
+    EXPECT(clear != std::string::npos);
+    if (clear == std::string::npos) continue;
+    EXPECT(run.log.substr(clear + 1) == "m" + repeat("g", 10) + "m" + "s");
+    expect_phase_numbers(run.res, phase, cfg, 1);  // the two marks are ordinals 0 and 1
+    for (const FlowResult& f : run.res.flows) EXPECT(f.iter_us.n == 0);
+  }
+}
+
+TEST(test_scripted_run_phase_non_participant) {
+  const int n = 3, iters = 10;
+  const Schedule s = make_pair_schedule(n, Direction::Uni);
+  const RunConfig cfg = scripted_config(iters, 2);
+  int cells = 0, idle = 0;
+  for (const Phase& phase : s.phases) {
+    if (phase.idle) {
+      // The diagonal reports 0 and posts nothing.
+      if (idle++ > 0) continue;
+      for (const ScriptedRun& run : scripted_phase(n, phase, cfg)) {
+        EXPECT(run.res.idle && run.res.seconds_per_iter == 0 && run.res.agg_gbs == 0 && run.res.flows.empty());
+        for (double v : run.res.rank_seconds) EXPECT(v == 0);
+        EXPECT(run.log.empty() && run.asked.empty());
+      }
+      continue;
+    }
+    if (!(phase.row == 0 && phase.col == 1) && !(phase.row == 2 && phase.col == 0)) continue;
+    ++cells;
+    const int out = 3 - phase.row - phase.col;
+    EXPECT(!phase.participates(out));
+    for (bool relay : {false, true}) {
+      const auto runs = scripted_phase(n, phase, cfg, 1, relay);
+      for (int me = 0; me < n; ++me) {
+        const ScriptedRun& run = runs[static_cast<size_t>(me)];
+        const PhaseResult& res = run.res;
+        const double slow = script_T(std::max(phase.row, phase.col), iters) / 1e3;
+        // A rank outside the cell posts and times it only on a transport that
+        // routes through it; its time is then its own, and in neither case
+        // does it take part in the phase's maximum or in a flow's.
+        EXPECT((me == out && !relay) == run.log.empty());
+        EXPECT_REL(res.rank_seconds[static_cast<size_t>(phase.row)], script_T(phase.row, iters) / 1e3);
+        EXPECT_REL(res.rank_seconds[static_cast<size_t>(phase.col)], script_T(phase.col, iters) / 1e3);
+        if (relay)
+          EXPECT_REL(res.rank_seconds[static_cast<size_t>(out)], script_T(out, iters) / 1e3);
+        else
+          EXPECT(res.rank_seconds[static_cast<size_t>(out)] == 0);
+        EXPECT_REL(res.seconds_per_iter, slow / iters);
+        EXPECT(res.flows.size() == 1);
+        if (res.flows.size() != 1) continue;
+        EXPECT_REL(res.flows[0].seconds, slow / iters);
+        EXPECT_REL(res.agg_gbs, static_cast<double>(cfg.bytes) / (slow / iters) / 1e9);
+        EXPECT(res.flows[0].iter_us.n == static_cast<size_t>(iters));
+        EXPECT_REL(res.flows[0].iter_us.mean * iters, script_T(phase.col, iters) * 1e3);
+      }
+    }
+  }
+  EXPECT(cells == 2 && idle == n);  // (0,1): the rank outside would be the slowest by script; (2,0): the sender is
+}
+
+// The host clock is not scripted: sync() on rank r takes at least
+// 2 ms * (r + 1), so lower bounds and structure are what can be asserted.
+class SlowSync final : public Transport {
+ public:
+  explicit SlowSync(Transport& t) : t_(&t) {}
+  std::string name() const override { return "slow-sync"; }
+  int rank() const override { return t_->rank(); }
+  int nranks() const override { return t_->nranks(); }
+  void* alloc(size_t b) override { return t_->alloc(b); }
+  void release(void* p) override { t_->release(p); }
+  void fill(void* p, size_t b, uint64_t s) override { t_->fill(p, b, s); }
+  void zero(void* p, size_t b) override { t_->zero(p, b); }
+  VerifyResult verify(const void* p, size_t b, uint64_t s) override { return t_->verify(p, b, s); }
+  void group_begin() override { t_->group_begin(); }
+  void send(const void* p, size_t b, int peer) override { t_->send(p, b, peer); }
+  void recv(void* p, size_t b, int peer) override { t_->recv(p, b, peer); }
+  void group_end() override { t_->group_end(); }
+  int mark() override { return t_->mark(); }
+  double elapsed_ms(int a, int b) override { return t_->elapsed_ms(a, b); }
+  void clear_marks() override { t_->clear_marks(); }
+  void sync() override {
+    std::this_thread::sleep_for(std::chrono::milliseconds(2 * (rank() + 1)));
+    t_->sync();
+  }
+
+ private:
+  Transport* t_;
+};
+
+TEST(test_wallclock_phase_lower_bounds) {
+  const int n = 3, iters = 5;
+  const Schedule s = make_pair_schedule(n, Direction::Uni);
+  const Phase* cell = nullptr;
+  for (const Phase& p : s.phases)
+    if (p.row == 0 && p.col == 1) cell = &p;
+  EXPECT(cell != nullptr);
+  if (!cell) return;
+  run_ranks(n, [&](Bootstrap& b, Transport& host) {
+    SlowSync t(host);
+    RunConfig cfg = scripted_config(iters, 0);
+    cfg.timing = Timing::Wallclock;
+    Buffers bufs(t, cfg.bytes, 1);
+    const PhaseResult res = run_phase(t, b, *cell, 0, cfg, bufs);
+    // Barrier-bracketed host clock: every rank, the one outside the cell
+    // included, waits for the slowest, whose every iteration syncs.
+    double most = 0;
+    for (double v : res.rank_seconds) {
+      EXPECT(v >= iters * 2e-3);
+      most = std::max(most, v);
+    }
+    EXPECT(res.rank_seconds[2] > 0);
+    EXPECT_REL(res.seconds_per_iter, most / iters);  // the maximum over ALL ranks
+    EXPECT(res.flows.size() == 1);
+    for (const FlowResult& f : res.flows) {
+      EXPECT_REL(f.seconds, res.seconds_per_iter);  // every flow carries the phase time
+      EXPECT_REL(f.gbs, static_cast<double>(cfg.bytes) / f.seconds / 1e9);
+      EXPECT(f.iter_us.n == static_cast<size_t>(iters));
+      EXPECT(f.iter_us.min >= 2e3 * (f.flow.dst + 1));
+      // The receiver's samples lie inside its window.
+      EXPECT(f.iter_us.mean * iters <= res.rank_seconds[static_cast<size_t>(f.flow.dst)] * 1e6 * (1 + 1e-12));
+    }
+    // This rank's wall clock brackets this rank's window (every rank checks
+    // its own: clocks of two ranks' barrier exits are not ordered).
+    EXPECT(res.wall_seconds >= res.rank_seconds[static_cast<size_t>(b.rank())]);
+    b.barrier();
+  });
+}
+
+TEST(test_scripted_latency) {
+  // Host-posted: the leader (lower rank) halves each mark-to-mark interval,
+  // the follower contributes nothing, and (a, b) carries rank a's summary.
+  const int n = 4, iters = 12;
+  run_ranks(n, [&](Bootstrap& b, Transport& host) {
+    ScriptedClock t(host);
+    Buffers bufs(t, 64, 1);
+    const auto lat = run_latency(t, b, 8, iters, 2, bufs);
+    EXPECT(lat.size() == 6);
+    for (const LatencyResult& l : lat) {
+      EXPECT(l.a < l.b && l.method == "host");
+      std::vector<double> want;
+      for (long i = 0; i < iters; ++i) want.push_back((script_T(l.a, i + 1) - script_T(l.a, i)) * 1e3 / 2);
+      expect_summary(l.one_way_us, want);
+    }
+    // n - 1 rounds; this rank leads against every higher rank and asks for
+    // nothing in the rounds it follows.
+    EXPECT(t.asked.size() == static_cast<size_t>(iters) * static_cast<size_t>(n - 1 - b.rank()));
+    for (const auto& q : t.asked) EXPECT(q.second == q.first + 1);
+    b.barrier();
+  });
+  // One rank: the self exchange is one way already, not halved.
+  {
+    auto boot = make_local_bootstrap();
+    TransportOptions opt;
+    opt.timeout_s = 60;
+    auto host = make_host_transport(*boot, opt);
+    ScriptedClock t(*host);
+    Buffers bufs(t, 64, 1);
+    const auto lat = run_latency(t, *boot, 8, iters, 2, bufs);
+    EXPECT(lat.size() == 1);
+    if (lat.size() == 1) {
+      EXPECT(lat[0].a == 0 && lat[0].b == 0);
+      std::vector<double> want;
+      for (long i = 0; i < iters; ++i) want.push_back((script_T(0, i + 1) - script_T(0, i)) * 1e3);
+      expect_summary(lat[0].one_way_us, want);
+    }
+  }
+  // Pre-posted behind a (faked) gate in batches of 8: every batch takes
+  // marks 0..k, its first exchange (the interval ending at mark 1) is not
+  // sampled, and batches overlap by one so exactly `iters` samples remain.
+  setenv("P2P_TEST_FAKE_GATE", "1", 1);
+  const int total = 37, batch = 8;
+  run_ranks(n, [&](Bootstrap& b, Transport& host) {
+    ScriptedClock t(host);
+    Buffers bufs(t, 64, 1);
+    const auto lat = run_latency(t, b, 8, total, 2, bufs, batch);
+    EXPECT(lat.size() == 6);
+    for (const LatencyResult& l : lat) {
+      EXPECT(l.method == "preposted");
+      std::vector<double> want;
+      for (int left = total; left > 0;) {
+        const int k = std::min(batch, left + 1);  // exchanges of this batch; k - 1 of them are sampled
+        for (long i = 2; i <= k; ++i) want.push_back((script_T(l.a, i) - script_T(l.a, i - 1)) * 1e3 / 2);
+        left -= k - 1;
+      }
+      EXPECT(want.size() == static_cast<size_t>(total));
+      expect_summary(l.one_way_us, want);
+    }
+    EXPECT(t.asked.size() == static_cast<size_t>(total) * static_cast<size_t>(n - 1 - b.rank()));
+    for (const auto& q : t.asked) EXPECT(q.second != 1 && q.second == q.first + 1);
+    b.barrier();
+  });
+  unsetenv("P2P_TEST_FAKE_GATE");
+}
+
+TEST(test_scripted_step_driver) {
+  // Every rank takes part in every step: step() takes two marks, run_steps
+  // one per boundary; a step's time is the interval of its recorded pair.
+  run_ranks(4, [&](Bootstrap& b, Transport& host) {
+    ScriptedClock t(host);
+    const int me = b.rank();
+    StepDriver d(t, b, make_tournament_schedule(4, Direction::Bi), 4100, 2, true, 21);
+    d.connect();
+    d.reset();
+    EXPECT(!t.log.empty() && t.log.back() == 'c');
+    long m = t.count('m');
+    d.step(0);
+    EXPECT(t.count('m') == m + 2);
+    d.step(1);
+    EXPECT(t.count('m') == m + 4);
+    d.run_steps(2, 4);
+    EXPECT(t.count('m') == m + 4 + 5);
+    d.sync();
+    t.asked.clear();
+    std::vector<double> ms = d.step_ms();
+    const std::vector<std::pair<int, int>> pairs{{0, 1}, {2, 3}, {4, 5}, {5, 6}, {6, 7}, {7, 8}};
+    EXPECT(t.asked == pairs);
+    EXPECT(ms.size() == pairs.size());
+    double chained = 0;
+    for (size_t k = 0; k < ms.size() && k < pairs.size(); ++k) {
+      EXPECT_REL(ms[k], script_T(me, pairs[k].second) - script_T(me, pairs[k].first));
+      if (k >= 2) chained += ms[k];
+    }
+    EXPECT_REL(chained, script_T(me, 8) - script_T(me, 4));  // chained steps tile their run
+    EXPECT(d.verify_steps(2, 4).mismatches == 0);
+    // reset(): ordinals restart, the next run starts from a fresh mark, and
+    // only the new steps are reported.
+    d.reset();
+    EXPECT(t.log.back() == 'c');
+    m = t.count('m');
+    d.run_steps(6, 2);
+    EXPECT(t.count('m') == m + 3);
+    d.sync();
+    t.asked.clear();
+    ms = d.step_ms();
+    const std::vector<std::pair<int, int>> fresh{{0, 1}, {1, 2}};
+    EXPECT(t.asked == fresh);
+    EXPECT(ms.size() == 2);
+    if (ms.size() == 2) {
+      EXPECT_REL(ms[0], script_T(me, 1));
+      EXPECT_REL(ms[1], script_T(me, 2) - script_T(me, 1));
+    }
+    b.barrier();
+  });
+  // The pair schedule on 3 ranks: every rank sits steps out (the diagonal,
+  // and the cells of the two others).  Those read 0.0, break the chain, and
+  // the step after one starts from a mark of its own.
+  run_ranks(3, [&](Bootstrap& b, Transport& host) {
+    ScriptedClock t(host);
+    const int me = b.rank();
+    const Schedule s = make_pair_schedule(3, Direction::Uni);
+    const long steps = static_cast<long>(s.phases.size());
+    EXPECT(steps == 9);
+    StepDriver d(t, b, s, 4100, 2, true, 22);
+    d.connect();
+    d.reset();
+    const long m = t.count('m');
+    d.run_steps(0, steps);
+    d.sync();
+    std::vector<double> want;
+    long next = 0, last = -1, sat_out = 0;
+    for (long k = 0; k < steps; ++k) {
+      if (!s.phases[static_cast<size_t>(k)].participates(me)) {
+        want.push_back(0.0);
+        last = -1;
+        ++sat_out;
+        continue;
+      }
+      const long a = last >= 0 ? last : next++;
+      const long z = next++;
+      want.push_back(script_T(me, z) - script_T(me, a));
+      last = z;
+    }
+    EXPECT(sat_out == 5);  // 3 diagonal cells and the 2 between the others
+    EXPECT(t.count('m') == m + next);
+    const std::vector<double> ms = d.step_ms();
+    EXPECT(ms.size() == want.size());
+    for (size_t k = 0; k < ms.size() && k < want.size(); ++k) {
+      if (want[k] == 0.0)
+        EXPECT(ms[k] == 0.0);
+      else
+        EXPECT_REL(ms[k], want[k]);
+    }
+    EXPECT(d.verify_steps(0, steps).mismatches == 0);
+    b.barrier();
+  });
+}
+
 // remote_slots: the k-th send to a peer meets the k-th receive from it.
 TEST(test_remote_slots_repeated_peer) {
   Schedule s = make_ring_schedule(2, Direction::Bi);
