@@ -21,6 +21,7 @@
 
 #include "common.hpp"
 #include "diagnose.hpp"
+#include "hip_check.hpp"
 #include "kernels.hpp"
 
 namespace p2p {
@@ -45,12 +46,6 @@ static_assert(kSlots * kDiagFields <= kBlock, "one thread flushes one field of o
 // Field order of DiagRecord; the LDS table keeps the same order in 32 bits
 // (a unit holds 8192 words), with both ends as word offsets into the unit.
 enum : int { kZero = 0, kOther = 1, kCand = 2, kFlipped = 8, kFirst = 9, kLast = 10 };
-
-#define HIP_OK(cmd)                                                                          \
-  do {                                                                                       \
-    hipError_t e_ = (cmd);                                                                   \
-    if (e_ != hipSuccess) P2P_FATAL(strfmt("HIP error %s: %s", #cmd, hipGetErrorString(e_))); \
-  } while (0)
 
 // Passed by value in the kernarg segment.
 struct CandArgs {
@@ -246,7 +241,7 @@ void launch_diagnose(const void* p, size_t bytes, uint64_t seed, const DiagCandi
   check_diagnose_args(cands, ncand, granule);
   if (!bytes) return;
   P2P_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, "diagnose: buffer must be 16-byte aligned");
-  HIP_OK(hipMemsetAsync(records, 0, diagnose_records(bytes, granule) * sizeof(DiagRecord), stream));
+  HIPCHECK(hipMemsetAsync(records, 0, diagnose_records(bytes, granule) * sizeof(DiagRecord), stream));
   CandArgs c{};
   c.n = ncand;
   for (int k = 0; k < ncand; ++k) {
@@ -262,31 +257,7 @@ void launch_diagnose(const void* p, size_t bytes, uint64_t seed, const DiagCandi
   const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min(units, cap)));
   diagnose_kernel<<<grid, kBlock, 0, stream>>>(static_cast<const uint4*>(p), nvec, seed, c, shift,
                                                static_cast<const uint8_t*>(p) + nvec * 16, tail, nvec * 16, records);
-  HIP_OK(hipGetLastError());
-}
-
-Diagnoser::~Diagnoser() {
-  if (dev_) (void)hipFree(dev_);
-  if (host_) (void)hipHostFree(host_);
-}
-
-size_t Diagnoser::enqueue(const void* p, size_t bytes, uint64_t seed, const DiagCandidate* cands, int ncand,
-                          size_t granule, hipStream_t stream, unsigned max_grid, bool readback) {
-  if (!granule) granule = diagnose_granule(bytes);
-  check_diagnose_args(cands, ncand, granule);
-  count_ = diagnose_records(bytes, granule);
-  if (count_ > cap_) {
-    if (dev_) HIP_OK(hipFree(dev_));
-    if (host_) HIP_OK(hipHostFree(host_));
-    dev_ = host_ = nullptr;
-    cap_ = std::max(count_, kMaxDiagRecords);
-    HIP_OK(hipMalloc(&dev_, sizeof(DiagRecord) * cap_));
-    HIP_OK(hipHostMalloc(&host_, sizeof(DiagRecord) * cap_, hipHostMallocDefault));
-  }
-  if (!count_) return granule;
-  launch_diagnose(p, bytes, seed, cands, ncand, granule, dev_, stream, max_grid);
-  if (readback) HIP_OK(hipMemcpyAsync(host_, dev_, sizeof(DiagRecord) * count_, hipMemcpyDeviceToHost, stream));
-  return granule;
+  HIPCHECK(hipGetLastError());
 }
 
 }  // namespace dev

@@ -126,30 +126,7 @@ namespace dev {
 // default, 16 workgroups per CU.
 void launch_diagnose(const void* p, size_t bytes, uint64_t seed, const DiagCandidate* cands, int ncand, size_t granule,
                      DiagRecord* records, hipStream_t stream, unsigned max_grid = 0);
-
-// Device records and their pinned host copy for one stream's user.  enqueue()
-// puts the kernel and ONE readback of the records on `stream`; records() is
-// valid once the caller has synchronised the stream, its own way.  Every call
-// must be synchronised before the next (the arrays may grow).
-class Diagnoser {
- public:
-  Diagnoser() = default;
-  Diagnoser(const Diagnoser&) = delete;
-  Diagnoser& operator=(const Diagnoser&) = delete;
-  ~Diagnoser();
-  // Returns the granule used (granule == 0: diagnose_granule(bytes)).
-  // readback = false leaves the records on the device (timing the kernel).
-  size_t enqueue(const void* p, size_t bytes, uint64_t seed, const DiagCandidate* cands, int ncand, size_t granule,
-                 hipStream_t stream, unsigned max_grid = 0, bool readback = true);
-  const DiagRecord* records() const { return host_; }
-  size_t count() const { return count_; }
-
- private:
-  DiagRecord* dev_ = nullptr;
-  DiagRecord* host_ = nullptr;
-  size_t cap_ = 0;
-  size_t count_ = 0;
-};
+// (device_checks.hpp Diagnoser owns the records and their host copy.)
 
 }  // namespace dev
 }  // namespace p2p

@@ -25,7 +25,9 @@
 #include <mutex>
 #include <vector>
 
+#include "block_split.hpp"
 #include "common.hpp"
+#include "hip_check.hpp"
 #include "kernels.hpp"
 
 namespace p2p {
@@ -67,12 +69,6 @@ constexpr int kMultiVerifyPerCu = 16;
 // per wave); tests/test_zz_perf_floors_gpu.py test_verify_staging_ab puts the
 // box's lds_over_stride on the PERF line (0.991: 1 GiB 0.973, 4 GiB 0.996).
 constexpr VerifyImpl kDefaultVerify = VerifyImpl::Lds8;
-
-#define HIP_OK(cmd)                                                                          \
-  do {                                                                                       \
-    hipError_t e_ = (cmd);                                                                   \
-    if (e_ != hipSuccess) P2P_FATAL(strfmt("HIP error %s: %s", #cmd, hipGetErrorString(e_))); \
-  } while (0)
 
 __device__ __forceinline__ uint4 prng_vec_k(uint32_t key, uint64_t vec_index) {
   const uint32_t lo = static_cast<uint32_t>(vec_index * 4);
@@ -351,6 +347,7 @@ struct MultiVerifyArgs {
 
 __global__ __launch_bounds__(kBlock) void multi_verify_lds_kernel(const MultiVerifyArgs a,
                                                                   VerifyAccum* __restrict__ scratch) {
+  // copy_workgroup's search, not shared: a helper changed this kernel's code.
   int lo = 0, hi = a.njobs - 1;  // largest job with block_begin[job] <= blockIdx.x
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -366,17 +363,19 @@ __global__ __launch_bounds__(kBlock) void multi_verify_lds_kernel(const MultiVer
   lds_block_commit<kLdsStages>(acc, scratch + static_cast<size_t>(job) * kVerifyShards, b);
 }
 
-// One workgroup (one wave) per job: reset its shards.
-__global__ __launch_bounds__(64) void multi_verify_reset_kernel(VerifyAccum* scratch) {
+// One workgroup (one wave) per job resets the job's shards (the single
+// verify is one job).
+__global__ __launch_bounds__(64) void verify_reset_kernel(VerifyAccum* scratch) {
   VerifyAccum* a = scratch + static_cast<size_t>(blockIdx.x) * kVerifyShards + threadIdx.x;
   a->mismatches = 0;
   a->checksum = 0;
   a->first_bad = ~0ull;
 }
 
-// One wave per job folds its shards into out[job].
-__global__ __launch_bounds__(64) void multi_verify_finalize_kernel(const VerifyAccum* __restrict__ scratch,
-                                                                   VerifyAccum* __restrict__ out) {
+// One wave per job folds the job's shards into out[job].  The single verify
+// passes out == scratch (totals in shard 0, launch_verify's contract), so the
+// pair is not __restrict__ and every lane reads its shard before the write.
+__global__ __launch_bounds__(64) void verify_finalize_kernel(const VerifyAccum* scratch, VerifyAccum* out) {
   const VerifyAccum& s = scratch[static_cast<size_t>(blockIdx.x) * kVerifyShards + threadIdx.x];
   unsigned long long m = s.mismatches, c = s.checksum, f = s.first_bad;
 #pragma unroll
@@ -385,36 +384,11 @@ __global__ __launch_bounds__(64) void multi_verify_finalize_kernel(const VerifyA
     c += __shfl_xor(c, off, 64);
     f = min(f, __shfl_xor(f, off, 64));
   }
+  __syncthreads();
   if (threadIdx.x == 0) {
     out[blockIdx.x].mismatches = m;
     out[blockIdx.x].checksum = c;
     out[blockIdx.x].first_bad = f;
-  }
-}
-
-__global__ void verify_reset_kernel(VerifyAccum* acc) {
-  if (threadIdx.x < kVerifyShards) {
-    acc[threadIdx.x].mismatches = 0;
-    acc[threadIdx.x].checksum = 0;
-    acc[threadIdx.x].first_bad = ~0ull;
-  }
-}
-
-// One wave folds the 64 shards into shard 0.
-__global__ __launch_bounds__(64) void verify_finalize_kernel(VerifyAccum* acc) {
-  const int l = threadIdx.x;
-  unsigned long long m = acc[l].mismatches, s = acc[l].checksum, f = acc[l].first_bad;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    m += __shfl_xor(m, off, 64);
-    s += __shfl_xor(s, off, 64);
-    f = min(f, __shfl_xor(f, off, 64));
-  }
-  __syncthreads();  // every lane has read its shard before shard 0 is overwritten
-  if (l == 0) {
-    acc[0].mismatches = m;
-    acc[0].checksum = s;
-    acc[0].first_bad = f;
   }
 }
 
@@ -434,13 +408,13 @@ unsigned grid_for(uint64_t units) { return static_cast<unsigned>(std::max<uint64
 
 int cu_count() {
   int d = 0;
-  HIP_OK(hipGetDevice(&d));
+  HIPCHECK(hipGetDevice(&d));
   auto& c = dev_cache();
   std::lock_guard<std::mutex> lk(c.mu);
   if (static_cast<int>(c.cus.size()) <= d) c.cus.resize(static_cast<size_t>(d) + 1, 0);
   if (!c.cus[static_cast<size_t>(d)]) {
     int v = 0;
-    HIP_OK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d));
+    HIPCHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d));
     c.cus[static_cast<size_t>(d)] = v > 0 ? v : 256;
   }
   return c.cus[static_cast<size_t>(d)];
@@ -495,14 +469,14 @@ void launch_fill(void* p, size_t bytes, uint64_t seed, hipStream_t stream, FillI
     const bool last = end == nvec;
     const unsigned grid = grid_for((end - begin + kBlockVecs - 1) / kBlockVecs);
     fill_grid_kernel<<<grid, kBlock, 0, stream>>>(vp, begin, end, seed, tp, last ? tail : 0, nvec * 16);
-    HIP_OK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     if (last) break;
   }
 }
 
 void launch_verify_reset(VerifyAccum* acc, hipStream_t stream) {
   verify_reset_kernel<<<1, 64, 0, stream>>>(acc);
-  HIP_OK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
 }
 
 namespace {
@@ -534,10 +508,10 @@ void launch_verify(const void* p, size_t bytes, uint64_t seed, VerifyAccum* acc,
       launch_verify_t<true>(vp, nvec, seed, tp, tail, acc, impl, g, stream);
     else
       launch_verify_t<false>(vp, nvec, seed, tp, tail, acc, impl, g, stream);
-    HIP_OK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
   }
-  verify_finalize_kernel<<<1, 64, 0, stream>>>(acc);
-  HIP_OK(hipGetLastError());
+  verify_finalize_kernel<<<1, 64, 0, stream>>>(acc, acc);
+  HIPCHECK(hipGetLastError());
 }
 
 void launch_multi_verify(const VerifyJob* jobs, int njobs, VerifyAccum* scratch, VerifyAccum* out,
@@ -550,7 +524,6 @@ void launch_multi_verify(const VerifyJob* jobs, int njobs, VerifyAccum* scratch,
     const int cnt = std::min(kMaxVerifyJobs, njobs - first);
     MultiVerifyArgs a{};
     a.njobs = cnt;
-    uint64_t need[kMaxVerifyJobs] = {0}, total = 0;
     for (int i = 0; i < cnt; ++i) {
       const VerifyJob& j = jobs[first + i];
       P2P_CHECK(reinterpret_cast<uintptr_t>(j.p) % 16 == 0, "verify: buffer must be 16-byte aligned");
@@ -558,49 +531,15 @@ void launch_multi_verify(const VerifyJob* jobs, int njobs, VerifyAccum* scratch,
       a.nvec[i] = j.bytes / 16;
       a.tail[i] = static_cast<uint32_t>(j.bytes - a.nvec[i] * 16);
       a.seed[i] = j.seed;
-      need[i] = std::max<uint64_t>(1, (a.nvec[i] + kChunkVecs - 1) / kChunkVecs);
-      total += need[i];
     }
-    uint32_t acc = 0;
-    for (int i = 0; i < cnt; ++i) {
-      a.block_begin[i] = acc;
-      const uint64_t share = total <= cap ? need[i] : std::max<uint64_t>(1, need[i] * cap / total);
-      acc += static_cast<uint32_t>(std::min(share, need[i]));
-    }
-    a.block_begin[cnt] = acc;
-    multi_verify_reset_kernel<<<cnt, 64, 0, stream>>>(scratch);
-    HIP_OK(hipGetLastError());
-    multi_verify_lds_kernel<<<acc, kBlock, 0, stream>>>(a, scratch);
-    HIP_OK(hipGetLastError());
-    multi_verify_finalize_kernel<<<cnt, 64, 0, stream>>>(scratch, out + first);
-    HIP_OK(hipGetLastError());
+    const uint32_t grid = split_blocks(a.nvec, cnt, kChunkVecs, cap, a.block_begin);
+    verify_reset_kernel<<<cnt, 64, 0, stream>>>(scratch);
+    HIPCHECK(hipGetLastError());
+    multi_verify_lds_kernel<<<grid, kBlock, 0, stream>>>(a, scratch);
+    HIPCHECK(hipGetLastError());
+    verify_finalize_kernel<<<cnt, 64, 0, stream>>>(scratch, out + first);
+    HIPCHECK(hipGetLastError());
   }
-}
-
-BatchVerifier::~BatchVerifier() {
-  if (scratch_) (void)hipFree(scratch_);
-  if (out_) (void)hipFree(out_);
-  if (host_) (void)hipHostFree(host_);
-}
-
-void BatchVerifier::reserve(int njobs, const std::function<void()>& drain) {
-  if (!scratch_) HIP_OK(hipMalloc(&scratch_, multi_verify_scratch_bytes()));
-  if (njobs <= cap_) return;
-  // The stream may still read the old arrays: the caller drains it first.
-  if (out_ || host_) drain();
-  if (out_) HIP_OK(hipFree(out_));
-  if (host_) HIP_OK(hipHostFree(host_));
-  out_ = host_ = nullptr;
-  cap_ = std::max(njobs, 2 * cap_);
-  HIP_OK(hipMalloc(&out_, sizeof(VerifyAccum) * static_cast<size_t>(cap_)));
-  HIP_OK(hipHostMalloc(&host_, sizeof(VerifyAccum) * static_cast<size_t>(cap_), hipHostMallocDefault));
-}
-
-void BatchVerifier::enqueue(const VerifyJob* jobs, int njobs, hipStream_t stream) {
-  if (njobs <= 0) return;
-  P2P_CHECK(scratch_ && njobs <= cap_, "BatchVerifier::enqueue: reserve(njobs) first");
-  launch_multi_verify(jobs, njobs, scratch_, out_, stream);
-  HIP_OK(hipMemcpyAsync(host_, out_, sizeof(VerifyAccum) * static_cast<size_t>(njobs), hipMemcpyDeviceToHost, stream));
 }
 
 // ------------------------------------------------------------ multi copy ----
@@ -798,8 +737,6 @@ template <class Op>
 uint32_t plan_copy_group(const Op* ops, int cnt, int max_blocks, CopyArgs& a) {
   a.nops = cnt;
   a.coherent = 0;
-  uint64_t need[kMaxCopyOps] = {0};
-  uint64_t total_need = 0;
   for (int i = 0; i < cnt; ++i) {
     const CopyOp& o = ops[i];
     P2P_CHECK(reinterpret_cast<uintptr_t>(o.src) % 16 == 0 && reinterpret_cast<uintptr_t>(o.dst) % 16 == 0,
@@ -809,28 +746,20 @@ uint32_t plan_copy_group(const Op* ops, int cnt, int max_blocks, CopyArgs& a) {
     a.nvec[i] = o.bytes / 16;
     a.tail[i] = static_cast<uint32_t>(o.bytes - a.nvec[i] * 16);
     if (o.coherent) a.coherent |= 1u << i;
-    need[i] = std::max<uint64_t>(1, (a.nvec[i] + kBlockVecs - 1) / kBlockVecs);
-    total_need += need[i];
   }
   const uint64_t cap = max_blocks > 0 ? static_cast<uint64_t>(max_blocks) : kMaxGrid;
-  uint32_t acc = 0;
-  for (int i = 0; i < cnt; ++i) {
-    a.block_begin[i] = acc;
-    uint64_t share = total_need <= cap ? need[i] : std::max<uint64_t>(1, need[i] * cap / total_need);
-    acc += static_cast<uint32_t>(std::min(share, need[i]));
-  }
-  a.block_begin[cnt] = acc;
+  const uint32_t grid = split_blocks(a.nvec, cnt, kBlockVecs, cap, a.block_begin);
   a.uniform = static_cast<int32_t>(a.block_begin[1] - a.block_begin[0]);
   for (int i = 1; i < cnt; ++i)
     if (a.block_begin[i + 1] - a.block_begin[i] != static_cast<uint32_t>(a.uniform)) a.uniform = 0;
-  return acc;
+  return grid;
 }
 
 void launch_copy_group(const CopyOp* ops, int cnt, hipStream_t stream, int max_blocks) {
   CopyArgs a{};
   const uint32_t grid = plan_copy_group(ops, cnt, max_blocks, a);
   multi_copy_kernel<<<grid, kBlock, 0, stream>>>(a);
-  HIP_OK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
 }
 
 void launch_copy_group(const CheckedCopyOp* ops, int cnt, hipStream_t stream, int max_blocks) {
@@ -842,7 +771,7 @@ void launch_copy_group(const CheckedCopyOp* ops, int cnt, hipStream_t stream, in
     a.check.record[i] = ops[i].record;
   }
   multi_copy_checked_kernel<<<grid, kBlock, 0, stream>>>(a);
-  HIP_OK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
 }
 
 uint64_t copy_blocks(size_t bytes) { return std::max<uint64_t>(1, (bytes / 16 + kBlockVecs - 1) / kBlockVecs); }
@@ -902,7 +831,7 @@ void launch_multi_copy(const CopyOp* ops, int nops, hipStream_t stream, int max_
 void launch_copy_check_reset(CopyCheck* records, int n, hipStream_t stream) {
   if (n <= 0) return;
   copy_check_reset_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, stream>>>(records, n);
-  HIP_OK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
 }
 
 void launch_multi_copy_checked(const CheckedCopyOp* ops, int nops, hipStream_t stream, int max_blocks) {

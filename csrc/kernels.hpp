@@ -36,7 +36,6 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 
 #include "prng.hpp"
 
@@ -90,39 +89,10 @@ void launch_verify(const void* p, size_t bytes, uint64_t seed, VerifyAccum* acc,
 // resetting).  Batches of kMaxVerifyJobs, three launches each (reset, the
 // LDS-DMA verify over all the batch's buffers, finalize); `scratch` holds
 // multi_verify_scratch_bytes() and is reused by every batch (stream order).
-struct VerifyJob {
-  const void* p;
-  size_t bytes;
-  uint64_t seed;
-};
+// VerifyJob is prng.hpp's; device_checks.hpp BatchVerifier owns the arrays.
 constexpr int kMaxVerifyJobs = 32;
 constexpr size_t multi_verify_scratch_bytes() { return verify_accum_bytes() * kMaxVerifyJobs; }
 void launch_multi_verify(const VerifyJob* jobs, int njobs, VerifyAccum* scratch, VerifyAccum* out, hipStream_t stream);
-
-// The device scratch, device results and pinned host results of
-// launch_multi_verify for one stream's user (a transport), grown on demand.
-// reserve() makes room for njobs results: should the arrays grow, it calls
-// `drain` first -- the stream may still read the old ones -- which is the
-// caller's own wait for its stream (the transports' is bounded and
-// abort-aware).  enqueue() then puts the batched verify and ONE
-// readback of every job's totals on `stream`; results() is valid once the
-// caller has synchronised the stream.
-class BatchVerifier {
- public:
-  BatchVerifier() = default;
-  BatchVerifier(const BatchVerifier&) = delete;
-  BatchVerifier& operator=(const BatchVerifier&) = delete;
-  ~BatchVerifier();
-  void reserve(int njobs, const std::function<void()>& drain);
-  void enqueue(const VerifyJob* jobs, int njobs, hipStream_t stream);  // after reserve(njobs)
-  const VerifyAccum* results() const { return host_; }
-
- private:
-  VerifyAccum* scratch_ = nullptr;
-  VerifyAccum* out_ = nullptr;
-  VerifyAccum* host_ = nullptr;
-  int cap_ = 0;
-};
 
 // Device attributes cached per device (CU count drives grid sizing).
 int cu_count();

@@ -67,4 +67,12 @@ struct VerifyResult {
   uint64_t first_bad = ~0ull;    // lowest mismatching byte offset, ~0 if none
 };
 
+// One buffer to check against stream `seed` (Transport::verify_many, the
+// batched verify kernel).
+struct VerifyJob {
+  const void* p = nullptr;
+  size_t bytes = 0;
+  uint64_t seed = 0;
+};
+
 }  // namespace p2p

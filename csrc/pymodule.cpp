@@ -27,6 +27,7 @@
 #include "app.hpp"
 #include "bootstrap.hpp"
 #include "common.hpp"
+#include "device_checks.hpp"
 #include "kernels.hpp"
 #include "provenance.hpp"
 #include "report.hpp"
@@ -267,23 +268,21 @@ class PyStepDriver {
 hipStream_t as_stream(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Kernel entry points on raw device pointers (torch tensors' data_ptr()).
-struct KernelScratch {
-  dev::VerifyAccum* d = nullptr;
-  dev::VerifyAccum* h = nullptr;
-  int device = -1;
-};
-KernelScratch& scratch() {
-  static KernelScratch s;
+// Every check's arrays live in one DeviceChecks per device, never destroyed:
+// a static destructor would free device memory after the HIP runtime shut
+// down.  Growing one waits on the stream passed in (stream_wait).
+DeviceChecks& checks_for_current_device() {
+  static auto* per_device = new std::vector<DeviceChecks*>();
   int dv = 0;
-  if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
-  if (s.device != dv) {
-    if (s.d) (void)hipFree(s.d);
-    if (s.h) (void)hipHostFree(s.h);
-    if (hipMalloc(&s.d, dev::verify_accum_bytes()) != hipSuccess) P2P_FATAL("hipMalloc failed");
-    if (hipHostMalloc(&s.h, sizeof(dev::VerifyAccum), hipHostMallocDefault) != hipSuccess) P2P_FATAL("hipHostMalloc failed");
-    s.device = dv;
-  }
-  return s;
+  HIPCHECK(hipGetDevice(&dv));
+  if (static_cast<int>(per_device->size()) <= dv) per_device->resize(static_cast<size_t>(dv) + 1, nullptr);
+  DeviceChecks*& c = (*per_device)[static_cast<size_t>(dv)];
+  if (!c) c = new DeviceChecks();
+  return *c;
+}
+
+StreamWait stream_wait(hipStream_t st) {
+  return [st] { HIPCHECK(hipStreamSynchronize(st)); };
 }
 
 dev::VerifyImpl verify_impl_arg(int impl) {
@@ -305,71 +304,36 @@ py::tuple device_verify(uintptr_t ptr, size_t bytes, uint64_t seed, int impl, bo
                         unsigned max_grid, int lds_stages) {
   const dev::VerifyImpl vi = verify_impl_arg(impl);
   lds_stages_arg(lds_stages);
-  KernelScratch& ks = scratch();
+  DeviceChecks& c = checks_for_current_device();
   hipStream_t st = as_stream(stream);
   {
     py::gil_scoped_release nogil;
-    dev::launch_verify_reset(ks.d, st);
-    dev::launch_verify(reinterpret_cast<const void*>(ptr), bytes, seed, ks.d, vi, check, st, max_grid, lds_stages);
-    if (hipMemcpyAsync(ks.h, ks.d, sizeof(dev::VerifyAccum), hipMemcpyDeviceToHost, st) != hipSuccess)
-      P2P_FATAL("hipMemcpyAsync failed");
-    if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
+    c.verify_enqueue(reinterpret_cast<const void*>(ptr), bytes, seed, st, vi, check, max_grid, lds_stages, true);
+    stream_wait(st)();
   }
-  return py::make_tuple(ks.h->mismatches, ks.h->checksum, ks.h->first_bad);
+  const VerifyResult r = c.verify_result();
+  return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
 
-// The batched verify on raw pointers: [(mismatches, checksum, first_bad)]
-// per (ptr, bytes, seed) job, one readback (dev::BatchVerifier, per device).
-// The verifiers are never destroyed (like KernelScratch): a static
-// destructor would free device memory after the HIP runtime shut down.
-py::list device_verify_many(const std::vector<std::tuple<uintptr_t, size_t, uint64_t>>& jobs, uintptr_t stream) {
-  static auto* per_device = new std::vector<dev::BatchVerifier*>();
-  int dv = 0;
-  if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
-  if (static_cast<int>(per_device->size()) <= dv) per_device->resize(static_cast<size_t>(dv) + 1, nullptr);
-  dev::BatchVerifier*& bv = (*per_device)[static_cast<size_t>(dv)];
-  if (!bv) bv = new dev::BatchVerifier();
-  std::vector<dev::VerifyJob> dj;
+// The batched verify on raw pointers, always the batched kernel:
+// [(mismatches, checksum, first_bad)] per (ptr, bytes, seed) job, one
+// readback; readback = false: stream-ordered launches only (timing with
+// events), nothing returned.
+py::list device_verify_many(const std::vector<std::tuple<uintptr_t, size_t, uint64_t>>& jobs, uintptr_t stream,
+                            bool readback) {
+  dev::BatchVerifier& bv = checks_for_current_device().batch();
+  std::vector<VerifyJob> dj;
   for (const auto& j : jobs) dj.push_back({reinterpret_cast<const void*>(std::get<0>(j)), std::get<1>(j), std::get<2>(j)});
   hipStream_t st = as_stream(stream);
-  {
-    py::gil_scoped_release nogil;
-    bv->reserve(static_cast<int>(dj.size()), [st] {
-      if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
-    });
-    bv->enqueue(dj.data(), static_cast<int>(dj.size()), st);
-    if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
-  }
   py::list out;
-  for (size_t i = 0; i < dj.size(); ++i)
-    out.append(py::make_tuple(bv->results()[i].mismatches, bv->results()[i].checksum, bv->results()[i].first_bad));
-  return out;
-}
-
-// Stream-ordered batched verify, no readback (timing with events): the
-// scratch and results live per device and grow with the job count.
-void device_verify_many_launch(const std::vector<std::tuple<uintptr_t, size_t, uint64_t>>& jobs, uintptr_t stream) {
-  struct Buffers {
-    dev::VerifyAccum* scratch = nullptr;
-    dev::VerifyAccum* out = nullptr;
-    int cap = 0;
-  };
-  static std::vector<Buffers> per_device;
-  int dv = 0;
-  if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
-  if (static_cast<int>(per_device.size()) <= dv) per_device.resize(static_cast<size_t>(dv) + 1);
-  Buffers& b = per_device[static_cast<size_t>(dv)];
-  const int n = static_cast<int>(jobs.size());
-  if (!b.scratch && hipMalloc(&b.scratch, dev::multi_verify_scratch_bytes()) != hipSuccess) P2P_FATAL("hipMalloc failed");
-  if (n > b.cap) {
-    if (hipStreamSynchronize(as_stream(stream)) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
-    if (b.out) (void)hipFree(b.out);
-    b.cap = std::max(n, 2 * b.cap);
-    if (hipMalloc(&b.out, sizeof(dev::VerifyAccum) * static_cast<size_t>(b.cap)) != hipSuccess) P2P_FATAL("hipMalloc failed");
+  {
+    py::gil_scoped_release nogil;
+    bv.enqueue(dj.data(), static_cast<int>(dj.size()), st, stream_wait(st), readback);
+    if (readback) stream_wait(st)();
   }
-  std::vector<dev::VerifyJob> dj;
-  for (const auto& j : jobs) dj.push_back({reinterpret_cast<const void*>(std::get<0>(j)), std::get<1>(j), std::get<2>(j)});
-  dev::launch_multi_verify(dj.data(), n, b.scratch, b.out, as_stream(stream));
+  for (size_t i = 0; readback && i < dj.size(); ++i)
+    out.append(py::make_tuple(bv.results()[i].mismatches, bv.results()[i].checksum, bv.results()[i].first_bad));
+  return out;
 }
 
 // ---- checked copy (kernels.hpp CheckedCopyOp) on raw pointers ----
@@ -392,29 +356,8 @@ std::vector<int> checked_record_indices(const std::vector<CheckedOpTuple>& ops) 
   return idx;
 }
 
-// Device records for the current device, grown on demand and never freed
-// (like KernelScratch).  Growing waits for the device: a launch-only caller
-// may still have work in flight on the old ones.
-dev::CopyCheck* checked_records(size_t n) {
-  static dev::CopyCheck* rec = nullptr;
-  static size_t cap = 0;
-  static int device = -1;
-  int dv = 0;
-  if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
-  if (device != dv || n > cap) {
-    if (rec) {
-      (void)hipDeviceSynchronize();
-      (void)hipFree(rec);
-    }
-    cap = std::max<size_t>({n, 2 * cap, 64});
-    if (hipMalloc(&rec, sizeof(dev::CopyCheck) * cap) != hipSuccess) P2P_FATAL("hipMalloc failed");
-    device = dv;
-  }
-  return rec;
-}
-
 std::vector<dev::CheckedCopyOp> checked_ops_arg(const std::vector<CheckedOpTuple>& ops, const std::vector<int>& idx,
-                                                dev::CopyCheck* rec, bool coherent) {
+                                                const DeviceChecks& checks, bool coherent) {
   std::vector<dev::CheckedCopyOp> v;
   for (const auto& o : ops) {
     dev::CheckedCopyOp c;
@@ -424,7 +367,7 @@ std::vector<dev::CheckedCopyOp> checked_ops_arg(const std::vector<CheckedOpTuple
     c.coherent = coherent;
     c.seed = std::get<3>(o);
     c.stream_offset = std::get<4>(o);
-    c.record = rec + (std::lower_bound(idx.begin(), idx.end(), std::get<5>(o)) - idx.begin());
+    c.record = checks.record(static_cast<size_t>(std::lower_bound(idx.begin(), idx.end(), std::get<5>(o)) - idx.begin()));
     v.push_back(c);
   }
   return v;
@@ -434,18 +377,16 @@ py::list device_copy_checked(const std::vector<CheckedOpTuple>& ops, uintptr_t s
                              int accumulate_launches) {
   if (accumulate_launches < 1) throw py::value_error("copy_checked: accumulate_launches is >= 1");
   const std::vector<int> idx = checked_record_indices(ops);
-  std::vector<dev::CopyCheck> host(idx.size());
+  std::vector<Transport::InlineCheck> host;
   if (!idx.empty()) {
-    dev::CopyCheck* rec = checked_records(idx.size());
-    const std::vector<dev::CheckedCopyOp> v = checked_ops_arg(ops, idx, rec, coherent);
+    DeviceChecks& c = checks_for_current_device();
     hipStream_t st = as_stream(stream);
     py::gil_scoped_release nogil;
-    dev::launch_copy_check_reset(rec, static_cast<int>(idx.size()), st);
+    c.records_begin(idx.size(), st, stream_wait(st));
+    const std::vector<dev::CheckedCopyOp> v = checked_ops_arg(ops, idx, c, coherent);
     for (int k = 0; k < accumulate_launches; ++k)
       dev::launch_multi_copy_checked(v.data(), static_cast<int>(v.size()), st, max_blocks);
-    if (hipMemcpyAsync(host.data(), rec, sizeof(dev::CopyCheck) * idx.size(), hipMemcpyDeviceToHost, st) != hipSuccess)
-      P2P_FATAL("hipMemcpyAsync failed");
-    if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
+    host = c.records_read(st, stream_wait(st));
   }
   py::list out;
   for (const auto& r : host) out.append(py::make_tuple(r.mismatches, r.first_bad));
@@ -497,30 +438,21 @@ py::tuple extent_py(const DiagExtent& e) {
                         e.cand[4], e.cand[5]);
 }
 
-// One per device, never destroyed (like KernelScratch).
-dev::Diagnoser* diagnoser() {
-  static auto* per_device = new std::vector<dev::Diagnoser*>();
-  int dv = 0;
-  if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");
-  if (static_cast<int>(per_device->size()) <= dv) per_device->resize(static_cast<size_t>(dv) + 1, nullptr);
-  dev::Diagnoser*& dg = (*per_device)[static_cast<size_t>(dv)];
-  if (!dg) dg = new dev::Diagnoser();
-  return dg;
-}
-
+// The kernel and, with readback, one copy of its records and the wait:
+// returns the damaged granules (none without readback: launch only).
 py::list device_diagnose(uintptr_t ptr, size_t bytes, uint64_t seed, const std::vector<py::tuple>& candidates,
-                         size_t granule, uintptr_t stream, unsigned max_grid) {
+                         size_t granule, uintptr_t stream, unsigned max_grid, bool readback) {
   const std::vector<DiagCandidate> c = candidates_arg(candidates);
   granule = granule_arg(granule, bytes);
-  dev::Diagnoser* dg = diagnoser();
+  dev::Diagnoser& dg = checks_for_current_device().diagnoser();
   hipStream_t st = as_stream(stream);
   {
     py::gil_scoped_release nogil;
-    dg->enqueue(reinterpret_cast<const void*>(ptr), bytes, seed, c.data(), static_cast<int>(c.size()), granule, st,
-                max_grid);
-    if (hipStreamSynchronize(st) != hipSuccess) P2P_FATAL("hipStreamSynchronize failed");
+    dg.enqueue(reinterpret_cast<const void*>(ptr), bytes, seed, c.data(), static_cast<int>(c.size()), granule, st,
+               stream_wait(st), max_grid, readback);
+    if (readback) stream_wait(st)();
   }
-  return records_py(dg->records(), dg->count());
+  return readback ? records_py(dg.records(), dg.count()) : py::list();
 }
 
 py::list merge_extents_py(const std::vector<py::tuple>& records, size_t bytes, size_t granule) {
@@ -869,9 +801,13 @@ PYBIND11_MODULE(_p2pcore, m) {
         "impl: 0 auto (= 1), 1 LDS-DMA staged (lds8), 2 register staged (stride).  max_grid > 0 caps the workgroup "
         "count; lds_stages 4 or 8 forces that LDS-staged kernel (0: by size).  Returns (mismatching words, "
         "checksum, first bad byte offset or 2**64-1).");
-  m.def("verify_many", &device_verify_many, py::arg("jobs"), py::arg("stream") = 0,
+  m.def("verify_many", [](const std::vector<std::tuple<uintptr_t, size_t, uint64_t>>& jobs, uintptr_t stream) {
+        return device_verify_many(jobs, stream, true);
+      }, py::arg("jobs"), py::arg("stream") = 0,
         "Batched verify of [(ptr, bytes, seed)]: one (mismatches, checksum, first_bad) per job, one readback.");
-  m.def("verify_many_launch", &device_verify_many_launch, py::arg("jobs"), py::arg("stream") = 0,
+  m.def("verify_many_launch", [](const std::vector<std::tuple<uintptr_t, size_t, uint64_t>>& jobs, uintptr_t stream) {
+        device_verify_many(jobs, stream, false);
+      }, py::arg("jobs"), py::arg("stream") = 0,
         "Stream-ordered batched verify launches only (timing).");
   m.def("verify_launch", [](uintptr_t ptr, size_t bytes, uint64_t seed, int impl, bool check, uintptr_t stream,
                             unsigned max_grid, int lds_stages) {
@@ -879,10 +815,8 @@ PYBIND11_MODULE(_p2pcore, m) {
         // for timing the kernel with events.
         const dev::VerifyImpl vi = verify_impl_arg(impl);
         lds_stages_arg(lds_stages);
-        KernelScratch& ks = scratch();
-        dev::launch_verify_reset(ks.d, as_stream(stream));
-        dev::launch_verify(reinterpret_cast<const void*>(ptr), bytes, seed, ks.d, vi, check, as_stream(stream), max_grid,
-                           lds_stages);
+        checks_for_current_device().verify_enqueue(reinterpret_cast<const void*>(ptr), bytes, seed, as_stream(stream), vi,
+                                                   check, max_grid, lds_stages, false);
       }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("impl") = 0, py::arg("check") = true,
       py::arg("stream") = 0, py::arg("max_grid") = 0, py::arg("lds_stages") = 0);
   m.def("copy", [](uintptr_t dst, uintptr_t src, size_t bytes, uintptr_t stream, int max_blocks, bool coherent) {
@@ -910,8 +844,9 @@ PYBIND11_MODULE(_p2pcore, m) {
         "(mismatching words, first bad stream byte or 2**64-1) per distinct record index, in ascending order.");
   m.def("copy_checked_launch", [](const std::vector<CheckedOpTuple>& ops, uintptr_t stream, bool coherent, int max_blocks) {
         const std::vector<int> idx = checked_record_indices(ops);
-        dev::CopyCheck* rec = checked_records(idx.size());
-        const std::vector<dev::CheckedCopyOp> v = checked_ops_arg(ops, idx, rec, coherent);
+        DeviceChecks& c = checks_for_current_device();
+        c.records_begin(idx.size(), as_stream(stream), stream_wait(as_stream(stream)), false);
+        const std::vector<dev::CheckedCopyOp> v = checked_ops_arg(ops, idx, c, coherent);
         dev::launch_multi_copy_checked(v.data(), static_cast<int>(v.size()), as_stream(stream), max_blocks);
       }, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0,
       "Stream-ordered launch of the checked copy only (timing with events): no reset, no readback.");
@@ -993,7 +928,10 @@ PYBIND11_MODULE(_p2pcore, m) {
   });
   // ---- mismatch diagnosis ----
   m.attr("MAX_DIAG_CANDIDATES") = kMaxDiagCandidates;
-  m.def("diagnose", &device_diagnose, py::arg("ptr"), py::arg("bytes"), py::arg("seed"),
+  m.def("diagnose", [](uintptr_t ptr, size_t bytes, uint64_t seed, const std::vector<py::tuple>& candidates,
+                       size_t granule, uintptr_t stream, unsigned max_grid) {
+        return device_diagnose(ptr, bytes, seed, candidates, granule, stream, max_grid, true);
+      }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"),
         py::arg("candidates") = std::vector<py::tuple>{}, py::arg("granule") = 0, py::arg("stream") = 0,
         py::arg("max_grid") = 0,
         "The gfx950 diagnosis kernel on a device buffer (blocking): the damaged granules, each (index, first_bad, "
@@ -1004,9 +942,7 @@ PYBIND11_MODULE(_p2pcore, m) {
                               size_t granule, uintptr_t stream, unsigned max_grid) {
         // Stream-ordered launch only (the records' memset + the kernel), no
         // readback: for timing the kernel with events.
-        const std::vector<DiagCandidate> c = candidates_arg(candidates);
-        diagnoser()->enqueue(reinterpret_cast<const void*>(ptr), bytes, seed, c.data(), static_cast<int>(c.size()),
-                             granule_arg(granule, bytes), as_stream(stream), max_grid, false);
+        device_diagnose(ptr, bytes, seed, candidates, granule, stream, max_grid, false);
       }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("candidates") = std::vector<py::tuple>{},
       py::arg("granule") = 0, py::arg("stream") = 0, py::arg("max_grid") = 0);
   m.def("host_diagnose", [](py::bytes data, uint64_t seed, const std::vector<py::tuple>& candidates, size_t granule) {

@@ -56,11 +56,7 @@ class Transport {
   // Blocking: result i == verify(jobs[i]).  GPU transports check the whole
   // list in batched launches with one readback and one sync (the post-timing
   // check of many receive slots); the default checks one buffer at a time.
-  struct VerifyJob {
-    const void* p = nullptr;
-    size_t bytes = 0;
-    uint64_t seed = 0;
-  };
+  using VerifyJob = p2p::VerifyJob;
   virtual std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs) {
     std::vector<VerifyResult> out;
     out.reserve(jobs.size());

@@ -54,9 +54,9 @@
 #include <thread>
 #include <vector>
 
-#include "batch_verify.hpp"
 #include "bootstrap.hpp"
 #include "common.hpp"
+#include "device_checks.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
 #include "provenance.hpp"
@@ -80,19 +80,17 @@ class IpcTransport final : public Transport {
  public:
   IpcTransport(Bootstrap& boot, const TransportOptions& opt)
       : boot_(boot), rank_(boot.rank()), n_(boot.size()), timeout_(opt.timeout_s), engine_(opt.ipc_engine),
-        relay_(engine_ == "relay"), push_(engine_ == "push" || relay_) {
+        relay_(engine_ == "relay"), push_(engine_ == "push" || relay_),
+        checks_(static_cast<dev::VerifyImpl>(opt.verify_impl)) {
     P2P_CHECK(engine_ == "kernel" || engine_ == "sdma" || engine_ == "push" || relay_,
               "ipc engine must be 'kernel', 'sdma', 'push' or 'relay'");
     if (relay_) route_opt_ = route_options_from_env();
-    verify_impl_ = static_cast<dev::VerifyImpl>(opt.verify_impl);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) P2P_FATAL("ipc transport: no HIP device visible");
     device_ = opt.device >= 0 ? opt.device : 0;
     P2P_CHECK(device_ < ndev, strfmt("rank %d wants GPU %d but only %d are visible", rank_, device_, ndev));
     HIPCHECK(hipSetDevice(device_));
     HIPCHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    HIPCHECK(hipMalloc(&acc_, dev::verify_accum_bytes()));
-    HIPCHECK(hipHostMalloc(&acc_host_, sizeof(dev::VerifyAccum), hipHostMallocDefault));
     hipDeviceProp_t prop;
     HIPCHECK(hipGetDeviceProperties(&prop, device_));
     desc_ = strfmt("hip:%d %s (%s, %d CUs) ipc-%s", device_, prop.name, prop.gcnArchName, prop.multiProcessorCount,
@@ -128,10 +126,6 @@ class IpcTransport final : public Transport {
     for (auto e : side_done_) (void)hipEventDestroy(e);
     if (fork_) (void)hipEventDestroy(fork_);
     for (auto ev : events_) (void)hipEventDestroy(ev);
-    if (acc_) (void)hipFree(acc_);
-    if (acc_host_) (void)hipHostFree(acc_host_);
-    if (check_dev_) (void)hipFree(check_dev_);
-    if (check_host_) (void)hipHostFree(check_host_);
     if (stream_) (void)hipStreamDestroy(stream_);
   }
 
@@ -197,31 +191,17 @@ class IpcTransport final : public Transport {
   void fill(void* p, size_t bytes, uint64_t seed) override { dev::launch_fill(p, bytes, seed, stream_); }
   void zero(void* p, size_t bytes) override { HIPCHECK(hipMemsetAsync(p, 0, bytes, stream_)); }
 
+  // The checks run on the stream behind the bounded, abort-aware sync()
+  // (device_checks.hpp).
   VerifyResult verify(const void* p, size_t bytes, uint64_t seed) override {
-    dev::launch_verify_reset(acc_, stream_);
-    dev::launch_verify(p, bytes, seed, acc_, verify_impl_, true, stream_);
-    HIPCHECK(hipMemcpyAsync(acc_host_, acc_, sizeof(dev::VerifyAccum), hipMemcpyDeviceToHost, stream_));
-    sync();
-    VerifyResult r;
-    r.mismatches = acc_host_->mismatches;
-    r.checksum = acc_host_->checksum;
-    r.first_bad = acc_host_->first_bad;
-    return r;
+    return checks_.verify(p, bytes, seed, stream_, [this] { sync(); });
   }
   std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs) override {
-    if (jobs.empty()) return {};
-    if ((verify_impl_ != dev::VerifyImpl::Auto && verify_impl_ != dev::VerifyImpl::Lds8) || !batch_verify_enabled())
-      return Transport::verify_many(jobs);
-    return batch_verify(batch_, jobs, stream_, [this] { sync(); });
+    return checks_.verify_many(jobs, stream_, [this] { sync(); });
   }
-  // The diagnosis kernel and one readback of its records, behind the same
-  // bounded, abort-aware wait.
   std::vector<DiagExtent> diagnose(const void* p, size_t bytes, uint64_t seed,
                                    const std::vector<DiagCandidate>& candidates) override {
-    const size_t granule =
-        diag_.enqueue(p, bytes, seed, candidates.data(), static_cast<int>(candidates.size()), 0, stream_);
-    sync();
-    return merge_extents(diag_.records(), diag_.count(), bytes, granule);
+    return checks_.diagnose(p, bytes, seed, candidates, stream_, [this] { sync(); });
   }
 
   // Buffer sets are registered collectively in the same order on every rank,
@@ -371,40 +351,19 @@ class IpcTransport final : public Transport {
   // each word it loads with the stream the sender filled (kernels.hpp
   // multi_copy_checked_kernel); one device record per delivery.
   bool supports_inline_check() const override { return engine_ == "kernel"; }
-  // The records and their pinned mirror grow on demand; the stream may still
-  // write the old ones, so it is drained first (bounded, abort-aware sync()),
-  // as BatchVerifier::reserve does.
   void inline_check_begin(size_t nrecords) override {
     P2P_CHECK(supports_inline_check(), "ipc transport: the inline check needs --ipc-engine kernel");
-    if (nrecords > check_cap_) {
-      if (check_dev_ || check_host_) sync();
-      if (check_dev_) HIPCHECK(hipFree(check_dev_));
-      if (check_host_) HIPCHECK(hipHostFree(check_host_));
-      check_dev_ = check_host_ = nullptr;
-      check_cap_ = std::max(nrecords, 2 * check_cap_);
-      HIPCHECK(hipMalloc(&check_dev_, sizeof(dev::CopyCheck) * check_cap_));
-      HIPCHECK(hipHostMalloc(&check_host_, sizeof(dev::CopyCheck) * check_cap_, hipHostMallocDefault));
-    }
-    check_n_ = nrecords;
-    dev::launch_copy_check_reset(check_dev_, static_cast<int>(nrecords), stream_);
+    checks_.records_begin(nrecords, stream_, [this] { sync(); });
   }
   void recv_checked(void* p, size_t bytes, int peer, size_t src_offset, uint64_t seed, size_t record_index) override {
     P2P_CHECK(supports_inline_check(), "ipc transport: the inline check needs --ipc-engine kernel");
     // A replayed graph would write the record it captured, whatever it delivers.
     P2P_CHECK(!capturing_, "ipc transport: no inline check inside a graph capture");
-    P2P_CHECK(record_index < check_n_, "ipc transport: inline_check_begin() first, with enough records");
+    P2P_CHECK(record_index < checks_.records(), "ipc transport: inline_check_begin() first, with enough records");
     post_recv(p, bytes, peer, src_offset, &seed, record_index);
   }
   std::vector<InlineCheck> inline_check_results() override {
-    std::vector<InlineCheck> out(check_n_);
-    if (!check_n_) return out;
-    HIPCHECK(hipMemcpyAsync(check_host_, check_dev_, sizeof(dev::CopyCheck) * check_n_, hipMemcpyDeviceToHost, stream_));
-    sync();
-    for (size_t i = 0; i < check_n_; ++i) {
-      out[i].mismatches = check_host_[i].mismatches;
-      out[i].first_bad = check_host_[i].first_bad;
-    }
-    return out;
+    return checks_.records_read(stream_, [this] { sync(); });
   }
 
   // A receive; with `seed`, one the kernel checks against that stream into
@@ -437,7 +396,7 @@ class IpcTransport final : public Transport {
         dev::CheckedCopyOp c;
         static_cast<dev::CopyOp&>(c) = op;
         c.seed = *seed;
-        c.record = check_dev_ + record_index;
+        c.record = checks_.record(record_index);
         checked_ops_.push_back(c);
       } else {
         ops_.push_back(op);
@@ -929,19 +888,12 @@ class IpcTransport final : public Transport {
   std::vector<hipStream_t> side_;
   std::vector<hipEvent_t> side_done_;
   hipEvent_t fork_ = nullptr;
-  dev::VerifyAccum* acc_ = nullptr;
-  dev::VerifyAccum* acc_host_ = nullptr;
-  dev::BatchVerifier batch_;
-  dev::Diagnoser diag_;
-  dev::VerifyImpl verify_impl_ = dev::VerifyImpl::Auto;
+  DeviceChecks checks_;  // verify, verify_many, diagnose; one record per checked delivery (inline_check_begin)
   std::string desc_;
   std::vector<Registration> regs_;
   bool in_group_ = false;
   std::vector<dev::CopyOp> ops_;
   std::vector<dev::CheckedCopyOp> checked_ops_;  // kernel engine: receives checked as they are copied
-  dev::CopyCheck* check_dev_ = nullptr;          // one record per checked delivery (inline_check_begin)
-  dev::CopyCheck* check_host_ = nullptr;         // pinned mirror, one readback
-  size_t check_cap_ = 0, check_n_ = 0;
   bool capturing_ = false;
   std::vector<std::array<int, 3>> covered_;  // relay: (src, dst, slot) posted by group_flows
   unsigned long long relayed_bytes_ = 0, relayed_stripes_ = 0;  // moved by this rank as a relay (P2P_RELAY_STATS)

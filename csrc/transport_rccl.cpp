@@ -60,9 +60,9 @@
 #include <thread>
 #include <vector>
 
-#include "batch_verify.hpp"
 #include "bootstrap.hpp"
 #include "common.hpp"
+#include "device_checks.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
 #include "provenance.hpp"
@@ -79,8 +79,8 @@ namespace {
 class RcclTransport final : public Transport {
  public:
   RcclTransport(Bootstrap& boot, const TransportOptions& opt)
-      : rank_(boot.rank()), n_(boot.size()), timeout_(opt.timeout_s) {
-    verify_impl_ = static_cast<dev::VerifyImpl>(opt.verify_impl);
+      : rank_(boot.rank()), n_(boot.size()), timeout_(opt.timeout_s),
+        checks_(static_cast<dev::VerifyImpl>(opt.verify_impl)) {
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0)
@@ -101,8 +101,6 @@ class RcclTransport final : public Transport {
     send_seq_.assign(static_cast<size_t>(n_), 0);
     recv_seq_.assign(static_cast<size_t>(n_), 0);
     touched_.assign(static_cast<size_t>(n_), 0);
-    HIPCHECK(hipMalloc(&acc_, dev::verify_accum_bytes()));
-    HIPCHECK(hipHostMalloc(&acc_host_, sizeof(dev::VerifyAccum), hipHostMallocDefault));
     open_communicators(boot, opt, ncomms);
     describe(ncomms);
   }
@@ -149,8 +147,6 @@ class RcclTransport final : public Transport {
     for (auto ev : cjoin_)
       if (ev) (void)hipEventDestroy(ev);
     if (fork_) (void)hipEventDestroy(fork_);
-    if (acc_) (void)hipFree(acc_);
-    if (acc_host_) (void)hipHostFree(acc_host_);
     if (recv_stream_) (void)hipStreamDestroy(recv_stream_);
     if (join_) (void)hipEventDestroy(join_);
     for (auto cs : cstreams_)
@@ -224,38 +220,21 @@ class RcclTransport final : public Transport {
     HIPCHECK(hipMemsetAsync(p, 0, bytes, stream_));
   }
 
+  // The checks run on the buffer stream behind the bounded, abort-aware
+  // sync() (device_checks.hpp).
   VerifyResult verify(const void* p, size_t bytes, uint64_t seed) override {
     buffer_work();
-    dev::launch_verify_reset(acc_, stream_);
-    dev::launch_verify(p, bytes, seed, acc_, verify_impl_, true, stream_);
-    HIPCHECK(hipMemcpyAsync(acc_host_, acc_, sizeof(dev::VerifyAccum), hipMemcpyDeviceToHost, stream_));
-    sync();
-    VerifyResult r;
-    r.mismatches = acc_host_->mismatches;
-    r.checksum = acc_host_->checksum;
-    r.first_bad = acc_host_->first_bad;
-    return r;
+    return checks_.verify(p, bytes, seed, stream_, [this] { sync(); });
   }
-
   std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs) override {
     if (jobs.empty()) return {};
-    // The batched kernel is the default LDS8 verify; another --verify-impl
-    // keeps the one-buffer path.
-    if ((verify_impl_ != dev::VerifyImpl::Auto && verify_impl_ != dev::VerifyImpl::Lds8) || !batch_verify_enabled())
-      return Transport::verify_many(jobs);
     buffer_work();
-    return batch_verify(batch_, jobs, stream_, [this] { sync(); });
+    return checks_.verify_many(jobs, stream_, [this] { sync(); });
   }
-
-  // The diagnosis kernel and one readback of its records on the buffer
-  // stream, behind the same bounded, abort-aware wait as the checks above.
   std::vector<DiagExtent> diagnose(const void* p, size_t bytes, uint64_t seed,
                                    const std::vector<DiagCandidate>& candidates) override {
     buffer_work();
-    const size_t granule =
-        diag_.enqueue(p, bytes, seed, candidates.data(), static_cast<int>(candidates.size()), 0, stream_);
-    sync();
-    return merge_extents(diag_.records(), diag_.count(), bytes, granule);
+    return checks_.diagnose(p, bytes, seed, candidates, stream_, [this] { sync(); });
   }
 
   void group_begin() override {
@@ -1009,11 +988,7 @@ class RcclTransport final : public Transport {
   std::vector<hipGraph_t> graphs_;
   std::vector<hipGraphExec_t> execs_;
   int next_event_ = 0;
-  dev::VerifyAccum* acc_ = nullptr;
-  dev::VerifyAccum* acc_host_ = nullptr;
-  dev::BatchVerifier batch_;
-  dev::Diagnoser diag_;
-  dev::VerifyImpl verify_impl_ = dev::VerifyImpl::Auto;
+  DeviceChecks checks_;
   std::string desc_;
   int hook_ = 0;
   std::atomic<bool> aborted_{false};  // abort_all ran: check_live refuses new work

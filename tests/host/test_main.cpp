@@ -19,6 +19,7 @@
 #include <unistd.h>
 
 #include "app.hpp"
+#include "block_split.hpp"
 #include "bootstrap.hpp"
 #include "common.hpp"
 #include "prng.hpp"
@@ -94,6 +95,61 @@ TEST(test_gbps_units) {
   // Reference: throughput = msg_size * 8. / time / 1e9 (p2p_matrix.cc:177)
   EXPECT_NEAR(gbps(33554432.0, 1e-3), 268.435456, 1e-9);
   EXPECT_NEAR(gbytes_per_s(33554432.0, 1e-3), 33.554432, 1e-12);
+}
+
+// --------------------------------------------------------- block split ----
+
+// split_blocks against its rule, written out: need = max(1, ceil(nvec /
+// block_vecs)); every job gets its need while the needs fit the cap, else
+// max(1, need * cap / total), never more than its need; block_begin holds the
+// prefix sums.
+static void expect_split(const std::vector<uint64_t>& nvec, uint64_t block_vecs, uint64_t cap) {
+  const int cnt = static_cast<int>(nvec.size());
+  std::vector<uint32_t> begin(nvec.size() + 1, 0xDEADu);
+  const uint32_t grid = split_blocks(nvec.data(), cnt, block_vecs, cap, begin.data());
+  std::vector<uint64_t> need(nvec.size());
+  uint64_t total = 0;
+  for (int i = 0; i < cnt; ++i) total += need[i] = std::max<uint64_t>(1, (nvec[i] + block_vecs - 1) / block_vecs);
+  uint64_t sum = 0;
+  for (int i = 0; i < cnt; ++i) {
+    EXPECT(begin[i] == sum);
+    EXPECT(begin[i + 1] >= begin[i]);
+    const uint64_t share = begin[i + 1] - begin[i];
+    EXPECT(share >= 1 && share <= need[i]);
+    if (total <= cap)
+      EXPECT(share == need[i]);
+    else
+      EXPECT(share == std::max<uint64_t>(1, need[i] * cap / total));
+    sum += share;
+  }
+  EXPECT(begin[cnt] == sum && grid == sum);
+}
+
+TEST(test_split_blocks) {
+  // One job: under the cap (its need, 3 blocks of 256 vectors), and over it.
+  expect_split({600}, 256, 1u << 20);
+  expect_split({600}, 256, 2);
+  // 32 equal jobs: equal shares (what plan_copy_group's `uniform` detects),
+  // under the cap and over it.
+  for (uint64_t cap : {uint64_t{1} << 20, uint64_t{4096}, uint64_t{40}}) {
+    std::vector<uint64_t> equal(32, (32u << 20) / 16);
+    expect_split(equal, 256, cap);
+    uint32_t begin[33];
+    split_blocks(equal.data(), 32, 256, cap, begin);
+    for (int i = 1; i < 32; ++i) EXPECT(begin[i + 1] - begin[i] == begin[1] - begin[0]);
+  }
+  // One huge job beside 31 one-block jobs under a small cap: the small ones
+  // keep their one block, the huge one is cut down.
+  std::vector<uint64_t> mixed(32, 100);
+  mixed[7] = (uint64_t{4} << 30) / 16;
+  expect_split(mixed, 256, 64);
+  expect_split(mixed, 2048, 4096);  // the batched verify's 32 KiB chunks, 16 workgroups x 256 CUs
+  // A zero-byte job needs one workgroup, alone and among others.
+  expect_split({0}, 256, 1u << 20);
+  expect_split({0, 4096, 0, 1}, 256, 1u << 20);
+  expect_split({0, 1u << 20, 0}, 256, 3);
+  uint32_t begin[2];
+  EXPECT(split_blocks(std::vector<uint64_t>{0}.data(), 1, 2048, 16, begin) == 1 && begin[0] == 0 && begin[1] == 1);
 }
 
 // --------------------------------------------------------------- stats ----
