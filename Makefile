@@ -26,7 +26,7 @@ HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
 CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks) kernels.o diagnose_hip.o pingpong.o)
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load) kernels.o diagnose_hip.o pingpong.o load_hip.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in
@@ -101,6 +101,10 @@ $(BUILD)/gpu/kernels.o: csrc/kernels.hip $(HEADERS) | $(BUILD)/gpu
 
 # csrc/diagnose.cpp (host side, in CORE) owns diagnose.o.
 $(BUILD)/gpu/diagnose_hip.o: csrc/diagnose.hip $(HEADERS) | $(BUILD)/gpu
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# csrc/load.cpp (BackgroundLoad, host side) owns load.o.
+$(BUILD)/gpu/load_hip.o: csrc/load.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/gpu/pingpong.o: csrc/pingpong.hip $(HEADERS) | $(BUILD)/gpu

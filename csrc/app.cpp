@@ -81,6 +81,13 @@ timing
                          of >= 1 MiB from a to b uses communicator (i + a + b) mod K on both
                          ends, smaller messages stay on the first (P2P_RCCL_SPLIT_MIN)  [1]
       --no-warm          do not pre-establish connections before timing
+      --load KIND[:WGS]  measure every (mode, dir, size) run once more while a load generator keeps
+                         each GPU busy: mfma (matrix cores: bf16 MFMA chains in registers) or
+                         hbm (streaming reads of a 256 MiB buffer), WGS workgroups of 256
+                         threads per launch [one per CU].  The quiet run comes first, exactly
+                         as without the option; the loaded one follows with each cell's ratio
+                         to quiet and the load's own rate alone and beside the transfer.
+                         --transport rccl | ipc; not with --reference or --resume
   -l, --latency          add a ping-pong latency matrix (with --mode ring also the dependent
                          ring token chain: per-hop latency of a pipeline 0 -> 1 -> ... -> 0)
       --device-latency   add a device-initiated ping-pong matrix (--transport ipc:
@@ -255,7 +262,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     static const char* kValued[] = {"-m", "--mode", "-d", "--dir", "-b", "--size", "--sizes", "-n", "--iters", "-w",
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
-                                    "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose"};
+                                    "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -339,6 +346,15 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       cfg->run.verify = true;
     } else if (a == "--diagnose") {
       cfg->run.diagnose = int_arg(0);
+    } else if (a == "--load") {
+      const std::string v = next();
+      std::string why;
+      if (!parse_load_spec(v, &cfg->load, &why)) {
+        std::fprintf(stderr, "p2p_matrix: --load '%s': %s (usage: --load mfma|hbm[:WGS], see --help)\n", v.c_str(),
+                     why.c_str());
+        *exit_code = 1;
+        return false;
+      }
     } else if (a == "--verify-impl") {
       const std::string v = next();
       std::string note;
@@ -424,6 +440,26 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     *exit_code = 1;
     return false;
   }
+  // --load needs a GPU to load, a quiet pass to compare with that is measured
+  // the same way, and a results file that holds both passes of every run.
+  if (cfg->load.on()) {
+    std::string with, why;
+    if (cfg->transport == "host" || cfg->transport == "shm") {
+      with = "--transport " + cfg->transport;
+      why = "it loads the GPU the transfer runs on, and this transport moves host memory without one";
+    } else if (cfg->reference_buffers) {  // set by --reference alone
+      with = "--reference";
+      why = "that is the reference's run on an idle GPU, with no warm-up to start the load behind";
+    } else if (cfg->resume) {
+      with = "--resume";
+      why = "it counts the runs already in the file, and a loaded run would count as its quiet one";
+    }
+    if (!why.empty()) {
+      std::fprintf(stderr, "p2p_matrix: --load cannot be combined with %s: %s\n", with.c_str(), why.c_str());
+      *exit_code = 1;
+      return false;
+    }
+  }
   // The inline check lives in the pull engine's own copy kernel; --no-verify
   // (no payload to compare with) switches it off again.
   if (!cfg->run.verify) cfg->run.inline_check = false;
@@ -437,6 +473,131 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     return false;
   }
   return true;
+}
+
+bool parse_load_spec(const std::string& text, LoadSpec* spec, std::string* err) {
+  const size_t colon = text.find(':');
+  const std::string kind = text.substr(0, colon);
+  if (kind != "mfma" && kind != "hbm") {
+    if (err) *err = "unknown kind '" + kind + "' (mfma | hbm)";
+    return false;
+  }
+  int wgs = 0;
+  if (colon != std::string::npos) {
+    const std::string v = text.substr(colon + 1);
+    char* end = nullptr;
+    const long x = std::strtol(v.c_str(), &end, 10);
+    if (v.empty() || *end || x < 1 || x > INT_MAX) {
+      if (err) *err = "WGS must be a whole number >= 1, got '" + v + "'";
+      return false;
+    }
+    wgs = static_cast<int>(x);
+  }
+  spec->kind = kind;
+  spec->wgs = wgs;
+  return true;
+}
+
+LoadSession open_load(Transport& t, Bootstrap& boot, const LoadSpec& spec) {
+  LoadSession ls;
+  const int n = boot.size(), me = boot.rank();
+  // Ranks sharing a GPU: the lowest one loads it.
+  const std::vector<std::string> keys = boot.allgather_string(t.device_key());
+  bool mine = !keys[static_cast<size_t>(me)].empty();
+  for (int r = 0; r < me && mine; ++r) mine = keys[static_cast<size_t>(r)] != keys[static_cast<size_t>(me)];
+  if (mine) ls.load = t.make_load(spec.kind, spec.wgs);
+  if (ls.load) ls.load->calibrate();
+  const double v[4] = {ls.load ? 1.0 : 0.0, ls.load ? static_cast<double>(ls.load->wgs()) : 0.0,
+                       ls.load ? ls.load->launch_s() : 0.0, ls.load ? ls.load->alone_rate() : 0.0};
+  std::vector<double> all(static_cast<size_t>(4 * n));
+  boot.allgather(v, all.data(), sizeof(v));
+  for (int r = 0; r < n; ++r) {
+    const double* a = &all[static_cast<size_t>(4 * r)];
+    if (a[0] == 0.0) continue;
+    ls.ranks.push_back(r);
+    ls.info.wgs = static_cast<int>(a[1]);
+    ls.info.launch_us += a[2] * 1e6;
+    ls.info.alone_rate += a[3];
+  }
+  P2P_CHECK(!ls.ranks.empty(), "--load: transport " + t.name() + " has no GPU to load");
+  ls.info.kind = spec.kind;
+  ls.info.unit = spec.kind == "mfma" ? "TFLOP/s" : "TB/s";
+  ls.info.launch_us /= static_cast<double>(ls.ranks.size());
+  ls.info.alone_rate /= static_cast<double>(ls.ranks.size());
+  return ls;
+}
+
+RunRecord run_loaded(Transport& t, Bootstrap& boot, const Schedule& s, const RunRecord& quiet, uint64_t salt,
+                     LoadSession& ls, Buffers& bufs, const PhaseCallback& on_phase) {
+  P2P_CHECK(quiet.phases.size() == s.phases.size(), "--load: the quiet record is not of this schedule");
+  RunRecord rec;
+  rec.mode = quiet.mode;
+  rec.dir = quiet.dir;
+  rec.bytes = quiet.bytes;
+  rec.repeat = quiet.repeat;
+  rec.cfg = quiet.cfg;
+  rec.cfg.salt = salt;
+  rec.load = ls.info;
+  BackgroundLoad* load = ls.load.get();
+  // The hooks fire once per non-idle phase, in schedule order.
+  size_t at = 0;
+  std::vector<LoadStats> stats;
+  RunConfig cfg = rec.cfg;
+  cfg.before_timing = [&] {
+    while (at < quiet.phases.size() && quiet.phases[at].idle) ++at;
+    P2P_CHECK(at < quiet.phases.size(), "--load: more phases than the quiet pass ran");
+    if (!load) return;
+    load->start(quiet.phases[at].hooked_seconds);
+    load->window_begin();
+  };
+  cfg.after_timing = [&] {
+    ++at;
+    if (!load) return;
+    load->window_end();
+    stats.push_back(load->stop());
+  };
+  rec.phases = run_schedule(t, boot, s, cfg, bufs, on_phase);
+
+  // Every rank's counters of every non-idle phase (zeros from a rank without
+  // a load), so each rank builds the same record.
+  constexpr size_t kF = 7;
+  size_t busy = 0;
+  for (const auto& ph : rec.phases) busy += ph.idle ? 0 : 1;
+  std::vector<double> mine(busy * kF, 0.0);
+  for (size_t k = 0; k < stats.size() && k < busy; ++k) {
+    const LoadStats& st = stats[k];
+    double* m = &mine[k * kF];
+    m[0] = 1.0;
+    m[1] = static_cast<double>(st.launches);
+    m[2] = static_cast<double>(st.launches_done);
+    m[3] = static_cast<double>(st.window_launches);
+    m[4] = st.window_s;
+    m[5] = st.during_rate;
+    m[6] = st.covered ? 1.0 : 0.0;
+  }
+  const std::vector<double> all = boot.allgather_vector(mine);
+  size_t k = 0;
+  for (size_t i = 0; i < rec.phases.size(); ++i) {
+    PhaseResult& ph = rec.phases[i];
+    if (ph.idle) continue;
+    PhaseLoad& l = ph.load;
+    l.present = true;
+    l.quiet_agg_gbs = quiet.phases[i].agg_gbs;
+    for (int r = 0; r < boot.size(); ++r) {
+      const double* m = &all[(static_cast<size_t>(r) * busy + k) * kF];
+      if (m[0] == 0.0) continue;
+      l.ranks.push_back(r);
+      l.launches += static_cast<long>(m[1]);
+      l.launches_done += static_cast<long>(m[2]);
+      l.window_launches += static_cast<long>(m[3]);
+      l.window_s = std::max(l.window_s, m[4]);
+      l.during_rate += m[5];
+      l.covered = l.covered && m[6] != 0.0;
+    }
+    if (!l.ranks.empty()) l.during_rate /= static_cast<double>(l.ranks.size());
+    ++k;
+  }
+  return rec;
 }
 
 namespace {
@@ -528,7 +689,8 @@ std::vector<uint8_t> open_results(const AppConfig& cfg, Bootstrap& boot, const s
 // Every (schedule, size) run; rank 0 prints the reference-format matrices of
 // pair runs as their cells finish (the reference prints and flushes per cell).
 void run_all(const AppConfig& cfg, Transport& t, Bootstrap& boot, const std::vector<Schedule>& scheds,
-             const std::vector<uint8_t>& skip, Buffers& bufs, std::ofstream& js, FILE* out, AppResult& res) {
+             const std::vector<uint8_t>& skip, Buffers& bufs, LoadSession* load, std::ofstream& js, FILE* out,
+             AppResult& res) {
   const int n = boot.size();
   const bool root = boot.rank() == 0;
   bool printed_compat = false;
@@ -568,6 +730,16 @@ void run_all(const AppConfig& cfg, Transport& t, Bootstrap& boot, const std::vec
           js.flush();
         }
         res.runs.push_back(std::move(rec));
+        // --load: the same run once more beside the load, appended.
+        if (load) {
+          RunRecord loaded = run_loaded(t, boot, s, res.runs.back(), static_cast<uint64_t>(res.runs.size()), *load, bufs);
+          for (const auto& ph : loaded.phases) res.mismatches += ph.total_mismatches;
+          if (js.is_open()) {
+            js << run_to_json(loaded, n) << "\n";
+            js.flush();
+          }
+          res.runs.push_back(std::move(loaded));
+        }
       }
     }
   }
@@ -646,7 +818,8 @@ void write_reports(const AppConfig& cfg, const Transport& t, const Bootstrap& bo
     std::ofstream cs(cfg.csv_path);
     P2P_CHECK(cs.good(), "cannot write " + cfg.csv_path);
     cs << csv_header();
-    for (const auto& rec : res.runs) cs << run_to_csv(rec);
+    for (const auto& rec : res.runs)
+      if (!rec.load.on()) cs << run_to_csv(rec);  // the CSV has no column for a load: quiet runs only
   }
   std::fflush(out);
 }
@@ -735,7 +908,7 @@ int count_slow_flows(const AppConfig& cfg, const AppResult& res, bool root) {
   for (const auto& rec : res.runs)
     for (const auto& ph : rec.phases)
       for (const auto& f : ph.flows)
-        if (f.flow.src != f.flow.dst && f.gbs < cfg.min_gbs) {
+        if (!rec.load.on() && f.flow.src != f.flow.dst && f.gbs < cfg.min_gbs) {  // the link check judges quiet runs
           ++slow;
           if (root)
             std::fprintf(stderr, "p2p_matrix: SLOW LINK: %d -> %d %.2f GB/s < %.2f (%s-%s, %s)\n", f.flow.src,
@@ -808,7 +981,11 @@ int run_app(const AppConfig& cfg, Bootstrap& boot, FILE* out, AppResult* result)
   AppResult& res = result ? *result : local;
   std::ofstream js;
   const std::vector<uint8_t> skip = open_results(cfg, boot, scheds, provenance, &js);
-  run_all(run_cfg, *t, boot, scheds, skip, bufs, js, out, res);
+  // --load: one calibrated load per GPU (after the transport, before it in
+  // destruction order).
+  LoadSession load;
+  if (cfg.load.on()) load = open_load(*t, boot, cfg.load);
+  run_all(run_cfg, *t, boot, scheds, skip, bufs, cfg.load.on() ? &load : nullptr, js, out, res);
   run_latencies(cfg, *t, boot, bufs, res);
   uint64_t fuzz_bad = 0;
   size_t fuzz_max = 0;

@@ -10,9 +10,11 @@
 #pragma once
 
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "background_load.hpp"
 #include "report.hpp"
 #include "runner.hpp"
 #include "schedule.hpp"
@@ -56,6 +58,7 @@ struct AppConfig {
   bool rccl_stock = false;   // --reference: RCCL's own kernel unroll (no P2P_RCCL_UNROLL)
   int comms = 1;             // RCCL communicators per rank (messages spread round-robin)
   int repeat = 1;            // --repeat R: every (mode, dir, size) run R times; repeat summary (median)
+  LoadSpec load;             // --load KIND[:WGS]: every run once more under a background GPU load
   int verbose = 0;
 };
 
@@ -88,6 +91,24 @@ struct AppResult {
   std::vector<std::string> link_matrix;
   std::vector<std::string> link_reports;
 };
+
+// ---- --load: the second, loaded pass of a run ----
+// The background loads of a job: one per GPU, on the lowest rank of those
+// that share it (Transport::device_key), calibrated.  Must be destroyed before
+// the transport it came from.
+struct LoadSession {
+  std::unique_ptr<BackgroundLoad> load;  // null on a rank that runs none
+  RunLoad info;                          // the same on every rank (rates: mean over the loads)
+  std::vector<int> ranks;                // the ranks that run a load
+};
+// Collective.  Fails where no rank's transport has a GPU to load.
+LoadSession open_load(Transport& t, Bootstrap& boot, const LoadSpec& spec);
+// Collective: `quiet`'s schedule and configuration once more (payload salt
+// `salt`), every non-idle phase bracketed by the load: start() with the quiet
+// phase's hooked seconds and window_begin() before the warm-up, window_end()
+// and stop() after the timed loop's sync.  Returns the loaded record.
+RunRecord run_loaded(Transport& t, Bootstrap& boot, const Schedule& s, const RunRecord& quiet, uint64_t salt,
+                     LoadSession& ls, Buffers& bufs, const PhaseCallback& on_phase = nullptr);
 
 // Runs everything collectively; rank 0 prints to `out`.  Returns 0 on success,
 // 2 if verification found corrupted data, 3 if a link ran below --min-gbs.

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <map>
 #include <memory>
 #include <string>
 #include <thread>
@@ -29,6 +30,7 @@
 #include "common.hpp"
 #include "device_checks.hpp"
 #include "kernels.hpp"
+#include "load.hpp"
 #include "provenance.hpp"
 #include "report.hpp"
 #include "runner.hpp"
@@ -89,6 +91,7 @@ class Session {
 
   ~Session() {
     teardown_outside_gil([this] {
+      loads_.clear();  // before the transport they came from
       t_.reset();
       boot_.reset();
     });
@@ -108,7 +111,10 @@ class Session {
   // One (mode, dir, size) run; returns the run JSON (report.cpp schema).
   std::string run(const std::string& mode, const std::string& dir, size_t bytes, int iters, int warmup,
                   const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
-                  int diagnose, bool inline_check) {
+                  int diagnose, bool inline_check, const std::string& load) {
+    LoadSpec load_spec;
+    std::string why;
+    P2P_CHECK(load.empty() || parse_load_spec(load, &load_spec, &why), "load '" + load + "': " + why);
     Schedule s = make_schedule(parse_mode(mode), parse_direction(dir), world());
     restrict_cells(&s, cells, true);
     RunConfig cfg;
@@ -138,7 +144,14 @@ class Session {
     rec.bytes = bytes;
     rec.cfg = cfg;
     rec.phases = run_schedule(*t_, *boot_, s, cfg, bufs);
-    return run_to_json(rec, world());
+    if (!load_spec.on()) return run_to_json(rec, world());
+    // load="mfma[:WGS]" | "hbm[:WGS]": the run once more beside a background
+    // load (app.hpp run_loaded); the loaded record is what comes back.
+    // One calibrated load per spec for the session's life: a run does not pay
+    // (or drift with) a fresh 256 MiB scratch and calibration each time.
+    auto it = loads_.find(load);
+    if (it == loads_.end()) it = loads_.emplace(load, open_load(*t_, *boot_, load_spec)).first;
+    return run_to_json(run_loaded(*t_, *boot_, s, rec, ++salt_, it->second, bufs), world());
   }
 
   std::string latency(size_t bytes, int iters, int warmup, int preposted) {
@@ -237,6 +250,7 @@ class Session {
   std::unique_ptr<Bootstrap> boot_;
   std::unique_ptr<Transport> t_;
   std::string transport_kind_;
+  std::map<std::string, LoadSession> loads_;  // run(load=): by spec text
   uint64_t salt_ = 1000;
 };
 
@@ -636,6 +650,74 @@ class HostWords {
   size_t n_;
 };
 
+// ---- the background-load kernels on raw pointers, and BackgroundLoad ----
+dev::LoadCtl load_ctl_arg(uintptr_t cancel, uintptr_t done, uintptr_t tickets, uint64_t ordinal) {
+  if (done && !tickets) throw py::value_error("load: done_ptr needs tickets_ptr (the launch's ticket counter)");
+  dev::LoadCtl c;
+  if (cancel) c.cancel = reinterpret_cast<const unsigned int*>(pointer_arg(cancel, 4, "load: cancel_ptr"));
+  if (done) c.done = reinterpret_cast<unsigned long long*>(pointer_arg(done, 8, "load: done_ptr"));
+  if (tickets) c.tickets = reinterpret_cast<unsigned long long*>(pointer_arg(tickets, 8, "load: tickets_ptr"));
+  c.ordinal = ordinal;
+  return c;
+}
+
+py::dict load_stats_py(const LoadStats& s) {
+  py::dict d;
+  d["launches"] = s.launches;
+  d["launches_done"] = s.launches_done;
+  d["window_launches"] = s.window_launches;
+  d["window_s"] = s.window_s;
+  d["during_rate"] = s.during_rate;
+  d["covered"] = s.covered;
+  return d;
+}
+
+// A load on the current device, as the GPU transports hand one out.
+class PyBackgroundLoad {
+ public:
+  PyBackgroundLoad(const std::string& kind, int wgs, double timeout_s) {
+    if (kind != "mfma" && kind != "hbm") throw py::value_error("BackgroundLoad: kind must be 'mfma' or 'hbm'");
+    if (wgs < 0) throw py::value_error("BackgroundLoad: wgs must be >= 1 (0: one per CU)");
+    load_ = make_background_load(kind, wgs, timeout_s);
+  }
+  ~PyBackgroundLoad() {
+    teardown_outside_gil([this] { load_.reset(); });
+  }
+  BackgroundLoad& l() { return *load_; }
+
+ private:
+  std::unique_ptr<BackgroundLoad> load_;
+};
+
+// report.hpp load_table of a hand-built loaded record: phases are dicts of
+// label, agg_gbs and the phase's "load" keys (docs/OUTPUT.md).
+std::string load_table_py(const std::string& kind, int wgs, double launch_us, double alone_rate, const std::string& unit,
+                          const std::vector<py::dict>& phases) {
+  RunRecord rec{};
+  rec.load.kind = kind;
+  rec.load.wgs = wgs;
+  rec.load.launch_us = launch_us;
+  rec.load.alone_rate = alone_rate;
+  rec.load.unit = unit;
+  for (const py::dict& d : phases) {
+    PhaseResult ph;
+    ph.label = d["label"].cast<std::string>();
+    ph.agg_gbs = d["agg_gbs"].cast<double>();
+    const py::dict l = d["load"].cast<py::dict>();
+    ph.load.present = true;
+    ph.load.quiet_agg_gbs = l["quiet_agg_gbs"].cast<double>();
+    ph.load.launches = l["launches"].cast<long>();
+    ph.load.launches_done = l["launches_done"].cast<long>();
+    ph.load.window_launches = l["window_launches"].cast<long>();
+    ph.load.window_s = l["window_s"].cast<double>();
+    ph.load.during_rate = l["during_rate"].cast<double>();
+    ph.load.covered = l["covered"].cast<bool>();
+    ph.load.ranks = l["ranks"].cast<std::vector<int>>();
+    rec.phases.push_back(ph);
+  }
+  return load_table(rec);
+}
+
 py::list schedule_py(const std::string& mode, const std::string& dir, int n) {
   Schedule s = make_schedule(parse_mode(mode), parse_direction(dir), n);
   py::list phases;
@@ -681,7 +763,8 @@ PYBIND11_MODULE(_p2pcore, m) {
       .def("run", &Session::run, py::arg("mode") = "pair", py::arg("dir") = "uni", py::arg("bytes") = 32u << 20,
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
            py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
-           py::arg("inline_check") = false, py::call_guard<NativeCall, py::gil_scoped_release>())
+           py::arg("inline_check") = false, py::arg("load") = "",
+           py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("device_latency", &Session::device_latency, py::arg("bytes") = 8, py::arg("iters") = 1000,
@@ -871,6 +954,66 @@ PYBIND11_MODULE(_p2pcore, m) {
       "The ping-pong kernel (launch only): role a as one wave, or a and b as the two waves of one workgroup.  A role "
       "is a dict of out_flag, out_payload, in_flag, in_payload, bytes, base, in_base, iters, leader, stamps, status, "
       "timeout_ticks (pointers as integers).");
+  m.def("load_mfma", [](int wgs, uint32_t reps, uint64_t seed, uintptr_t out_ptr, uintptr_t stream, uintptr_t cancel_ptr,
+                        uintptr_t done_ptr, uintptr_t tickets_ptr, uint64_t ordinal) {
+        if (wgs < 1) throw py::value_error("load_mfma: wgs must be at least 1");
+        const dev::LoadCtl ctl = load_ctl_arg(cancel_ptr, done_ptr, tickets_ptr, ordinal);
+        dev::launch_load_mfma(wgs, reps, seed, reinterpret_cast<float*>(pointer_arg(out_ptr, 16, "load_mfma: out_ptr")), ctl,
+                              as_stream(stream));
+      }, py::arg("wgs"), py::arg("reps"), py::arg("seed"), py::arg("out_ptr"), py::arg("stream") = 0,
+      py::arg("cancel_ptr") = 0, py::arg("done_ptr") = 0, py::arg("tickets_ptr") = 0, py::arg("ordinal") = 0,
+      "The matrix-core load kernel (launch only): wgs workgroups of 4 waves, each wave reps pairs of +A.B / -A.B bf16 "
+      "MFMAs and a final +A.B, its 32x32 f32 tile stored at out[(wg * 4 + wave) * 1024 + lane * 16 + reg] (wgs * 4096 "
+      "floats).  cancel_ptr: a 32-bit host-pinned word, non-zero makes every workgroup return without touching out; "
+      "done_ptr: a 64-bit host-pinned word that becomes ordinal + 1 when the launch's last workgroup ends; tickets_ptr: "
+      "the 64-bit device counter (0 between launches) that finds that workgroup.");
+  m.def("load_hbm", [](uintptr_t ptr, size_t bytes, uint32_t passes, int wgs, uintptr_t out_ptr, uintptr_t stream,
+                       uintptr_t cancel_ptr, uintptr_t done_ptr, uintptr_t tickets_ptr, uint64_t ordinal) {
+        if (wgs < 1) throw py::value_error("load_hbm: wgs must be at least 1");
+        if (!bytes || bytes % 4096) throw py::value_error("load_hbm: bytes must be a positive multiple of 4096");
+        const dev::LoadCtl ctl = load_ctl_arg(cancel_ptr, done_ptr, tickets_ptr, ordinal);
+        dev::launch_load_hbm(reinterpret_cast<const void*>(pointer_arg(ptr, 16, "load_hbm: ptr")), bytes, passes, wgs,
+                             reinterpret_cast<unsigned long long*>(pointer_arg(out_ptr, 8, "load_hbm: out_ptr")), ctl,
+                             as_stream(stream));
+      }, py::arg("ptr"), py::arg("bytes"), py::arg("passes"), py::arg("wgs"), py::arg("out_ptr"), py::arg("stream") = 0,
+      py::arg("cancel_ptr") = 0, py::arg("done_ptr") = 0, py::arg("tickets_ptr") = 0, py::arg("ordinal") = 0,
+      "The HBM-streaming load kernel (launch only): wgs workgroups read the buffer passes times with non-temporal 16 B "
+      "loads; out[wg] is the 64-bit sum of the 32-bit words that workgroup read.  cancel_ptr, done_ptr, tickets_ptr and "
+      "ordinal as in load_mfma.");
+  m.def("load_plan", [](double expected_s, double launch_s) {
+        const LoadPlan p = load_plan(expected_s, launch_s);
+        return py::make_tuple(p.launches, p.covers_s);
+      }, py::arg("expected_s"), py::arg("launch_s"),
+      "The train BackgroundLoad.start enqueues: (launches, seconds they cover) = ceil(2 expected_s / launch_s) launches, "
+      "at least 1 and at most MAX_LOAD_LAUNCHES.");
+  m.attr("MAX_LOAD_LAUNCHES") = kMaxLoadLaunches;
+  m.def("load_table", &load_table_py, py::arg("kind"), py::arg("wgs"), py::arg("launch_us"), py::arg("alone_rate"),
+        py::arg("unit"), py::arg("phases"),
+        "The lines the extended tables add for a loaded run (--load), from a run's \"load\" object and its phases "
+        "(dicts with label, agg_gbs and load).");
+  py::class_<PyBackgroundLoad>(m, "BackgroundLoad")
+      .def(py::init<const std::string&, int, double>(), py::arg("kind"), py::arg("wgs") = 0, py::arg("timeout_s") = 30.0,
+           py::call_guard<NativeCall, py::gil_scoped_release>())
+      .def("calibrate", [](PyBackgroundLoad& b) { b.l().calibrate(); }, py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Sizes one launch to about 250 us and measures the load alone (blocking).")
+      .def_property_readonly("kind", [](PyBackgroundLoad& b) { return b.l().kind(); })
+      .def_property_readonly("wgs", [](PyBackgroundLoad& b) { return b.l().wgs(); })
+      .def_property_readonly("unit", [](PyBackgroundLoad& b) { return std::string(b.l().unit()); })
+      .def_property_readonly("launch_s", [](PyBackgroundLoad& b) { return b.l().launch_s(); })
+      .def_property_readonly("alone_rate", [](PyBackgroundLoad& b) { return b.l().alone_rate(); })
+      .def("start", [](PyBackgroundLoad& b, double expected_s) { b.l().start(expected_s); }, py::arg("expected_s"),
+           py::call_guard<NativeCall, py::gil_scoped_release>())
+      .def("window_begin", [](PyBackgroundLoad& b) { b.l().window_begin(); })
+      .def("window_end", [](PyBackgroundLoad& b) { b.l().window_end(); })
+      .def("stop", [](PyBackgroundLoad& b) {
+             LoadStats s;
+             {
+               NativeCall in_engine;
+               py::gil_scoped_release nogil;
+               s = b.l().stop();
+             }
+             return load_stats_py(s);
+           }, "Cancels the queued launches, waits for the stream and returns the counters as a dict.");
   m.def("wall_clock_hz", []() {
         int dv = 0;
         if (hipGetDevice(&dv) != hipSuccess) P2P_FATAL("no HIP device");

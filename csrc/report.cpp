@@ -110,10 +110,10 @@ std::vector<std::string> fabric_findings(const std::vector<double>& uni, const s
 void print_fabric_check(FILE* out, const std::vector<RunRecord>& runs, int n) {
   if (n < 2) return;
   for (const auto& u : runs) {
-    if (u.mode != Mode::Pair || u.dir != Direction::Uni) continue;
+    if (u.mode != Mode::Pair || u.dir != Direction::Uni || u.load.on()) continue;
     const RunRecord* b = nullptr;
     for (const auto& r : runs)
-      if (r.mode == Mode::Pair && r.dir == Direction::Bi && r.bytes == u.bytes) b = &r;
+      if (r.mode == Mode::Pair && r.dir == Direction::Bi && r.bytes == u.bytes && !r.load.on()) b = &r;
     const auto ug = flow_matrix_gbs(u, n);
     std::vector<double> bg;
     if (b) bg = flow_matrix_gbs(*b, n);
@@ -128,6 +128,7 @@ void print_fabric_check(FILE* out, const std::vector<RunRecord>& runs, int n) {
 std::vector<RepeatSummary> repeat_summaries(const std::vector<RunRecord>& runs, int n) {
   std::vector<RepeatSummary> out;
   for (const auto& r : runs) {
+    if (r.load.on()) continue;  // the quiet passes are what repeats compare
     double v = 0;
     if (r.mode == Mode::Pair) {
       double sum = 0;
@@ -176,10 +177,55 @@ void print_repeat_summary(FILE* out, const std::vector<RepeatSummary>& sums) {
   std::fflush(out);
 }
 
+namespace {
+std::string ranks_text(const std::vector<int>& ranks) {
+  std::string o;
+  for (size_t i = 0; i < ranks.size(); ++i) o += strfmt("%s%d", i ? "," : "", ranks[i]);
+  return o;
+}
+
+}  // namespace
+
+// The loaded pass: every cell against its quiet rate, then the load's rate
+// alone against its rate inside the windows (weighted by their lengths).
+std::string load_table(const RunRecord& rec) {
+  std::string out;
+  long win = 0, launches = 0, done = 0;
+  double rate_sum = 0, win_s = 0;
+  bool covered = true;
+  const PhaseLoad* any = nullptr;
+  for (const auto& ph : rec.phases) {
+    if (!ph.load.present) continue;
+    const PhaseLoad& l = ph.load;
+    any = &l;
+    out += strfmt("  under load, '%s': %.2f GB/s = %.3f x quiet %.2f GB/s\n", ph.label.c_str(), ph.agg_gbs,
+                  l.quiet_agg_gbs > 0 ? ph.agg_gbs / l.quiet_agg_gbs : 0.0, l.quiet_agg_gbs);
+    win += l.window_launches;
+    launches += l.launches;
+    done += l.launches_done;
+    win_s += l.window_s;
+    rate_sum += l.during_rate * l.window_s;
+    covered = covered && l.covered;
+  }
+  if (!any) return out;
+  const double during = win_s > 0 ? rate_sum / win_s : 0.0;
+  out += strfmt(
+      "  load %s, %d workgroups, %.0f us launches on rank(s) %s: alone %.3f %s, during the windows %.3f %s "
+      "(%.3f x); %ld launches in %.4f s of windows (%ld of %ld enqueued ran)\n",
+      rec.load.kind.c_str(), rec.load.wgs, rec.load.launch_us, ranks_text(any->ranks).c_str(), rec.load.alone_rate,
+      rec.load.unit.c_str(), during, rec.load.unit.c_str(), rec.load.alone_rate > 0 ? during / rec.load.alone_rate : 0.0, win,
+      win_s, done, launches);
+  if (!covered)
+    out += "  WARNING: the load's train ran out before a window ended: part of that window ran on a quiet GPU "
+           "(\"covered\": false in --json)\n";
+  return out;
+}
+
 void print_extended(FILE* out, const RunRecord& rec, int n) {
   std::string head = strfmt("[%s %s | %s x %d | timing=%s warmup=%d%s]", mode_name(rec.mode), direction_name(rec.dir),
                             format_size(rec.bytes).c_str(), rec.cfg.iters, timing_name(rec.cfg.timing), rec.cfg.warmup,
                             rec.cfg.verify ? " verify" : "");
+  if (rec.load.on()) head.insert(head.size() - 1, strfmt(" load=%s:%d", rec.load.kind.c_str(), rec.load.wgs));
   std::fprintf(out, "\n== %s ==\n", head.c_str());
   bool blank_diag = rec.mode != Mode::Self && n > 1;
   auto gbs = flow_matrix_gbs(rec, n);
@@ -229,6 +275,7 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
                  in_bad ? "FAILED" : "OK", static_cast<unsigned long long>(in_bad),
                  static_cast<unsigned long long>(in_flight), static_cast<unsigned long long>(timed));
   }
+  if (rec.load.on()) std::fputs(load_table(rec).c_str(), out);
   // Phases whose warmup did not verify and were re-posted with smaller ops.
   for (const auto& ph : rec.phases)
     if (!ph.rechunked_to.empty())
@@ -337,6 +384,10 @@ std::string run_to_json(const RunRecord& rec, int n) {
     << (rec.cfg.verify ? "true" : "false") << ",\"timed_msgs\":" << timed << ",\"verified_msgs\":" << checked
     << ",\"verify_coverage\":" << (rec.cfg.verify && timed ? num(static_cast<double>(checked) / static_cast<double>(timed)) : "null")
     << ",\"rechunked\":" << (rechunked ? "true" : "false");
+  if (rec.load.on())  // the loaded pass of --load only
+    o << ",\"load\":{\"kind\":\"" << json_escape(rec.load.kind) << "\",\"wgs\":" << rec.load.wgs
+      << ",\"launch_us\":" << num(rec.load.launch_us) << ",\"alone_rate\":" << num(rec.load.alone_rate)
+      << ",\"unit\":\"" << json_escape(rec.load.unit) << "\"}";
   if (rec.cfg.inline_check) {  // present only when the option is on
     uint64_t in_flight = 0, in_bad = 0;
     std::vector<const PhaseResult*> phs;
@@ -372,6 +423,13 @@ std::string run_to_json(const RunRecord& rec, int n) {
     }
     o << "]";
     if (rec.cfg.inline_check) o << inline_json(ph.inline_msgs, ph.inline_mismatches, ph.timed_msgs, {&ph});
+    if (ph.load.present) {
+      const PhaseLoad& l = ph.load;
+      o << ",\"load\":{\"quiet_agg_gbs\":" << num(l.quiet_agg_gbs) << ",\"launches\":" << l.launches
+        << ",\"launches_done\":" << l.launches_done << ",\"window_launches\":" << l.window_launches
+        << ",\"window_s\":" << num(l.window_s) << ",\"during_rate\":" << num(l.during_rate)
+        << ",\"covered\":" << (l.covered ? "true" : "false") << ",\"ranks\":[" << ranks_text(l.ranks) << "]}";
+    }
     // RunConfig::diagnose: present only when something was found.
     if (!ph.diagnosis.empty()) {
       o << ",\"diagnosis\":[";

@@ -35,6 +35,16 @@ class CompatPrinter {
 // flow; bi = sum of both directions (p2p_matrix.cc:258 "* 2").
 double compat_cell_gbps(const PhaseResult& r);
 
+// --load: what the loaded pass of a run ran beside (empty kind: a quiet run).
+struct RunLoad {
+  std::string kind;       // "mfma" | "hbm"
+  int wgs = 0;            // workgroups per launch
+  double launch_us = 0;   // one launch alone
+  double alone_rate = 0;  // the load alone, per GPU, in `unit`
+  std::string unit;       // "TFLOP/s" | "TB/s"
+  bool on() const { return !kind.empty(); }
+};
+
 struct RunRecord {
   Mode mode;
   Direction dir;
@@ -42,6 +52,7 @@ struct RunRecord {
   RunConfig cfg;
   std::vector<PhaseResult> phases;
   int repeat = 0;  // --repeat: which run of this (mode, dir, size), 0-based
+  RunLoad load;    // --load: set on the loaded pass, which follows its quiet one
 };
 
 // N x N (row = src, col = dst) matrices built from all flows of a run.
@@ -60,6 +71,10 @@ std::vector<std::string> fabric_findings(const std::vector<double>& uni, const s
 
 // Human-readable tables appended after the compat section.
 void print_extended(FILE* out, const RunRecord& rec, int n);
+// The lines print_extended adds for the loaded pass of --load: every phase's
+// rate against its quiet one, the load's rate alone against its rate inside
+// the windows, and a warning when a train ran out before its window ended.
+std::string load_table(const RunRecord& rec);
 // The fabric lines of every pair-mode size with both a uni and a bi run
 // (fabric_findings), after the extended tables.
 void print_fabric_check(FILE* out, const std::vector<RunRecord>& runs, int n);

@@ -570,8 +570,10 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
     }
   } cap{t, t.chunk_cap()};
 
+  if (active) prepare_payload(t, phase, cfg, bufs, gens);
+  const double hooked0 = now_seconds();
+  if (cfg.before_timing) cfg.before_timing();
   if (active) {
-    prepare_payload(t, phase, cfg, bufs, gens);
     for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens);
     t.sync();
   }
@@ -672,6 +674,8 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   }
   const double w1 = now_seconds();
   res.wall_seconds = w1 - w0;
+  if (cfg.after_timing) cfg.after_timing();
+  res.hooked_seconds = now_seconds() - hooked0;
   if (skip || skip_some) t.set_discard(false);
 
   // The inline records, read once after the timed sync and before the check

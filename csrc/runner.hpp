@@ -69,6 +69,14 @@ struct RunConfig {
   // the check of the slots after timing runs as always.  Warm-up iterations
   // are posted unchecked.  Off: nothing changes.
   bool inline_check = false;
+  // Hooks around what a phase measures (--load brackets it with a background
+  // load): run_phase calls them on every rank of a non-idle phase, in both
+  // timings.  before_timing: after the payload and the poison are posted,
+  // before the first warm-up iteration.  after_timing: after the timed loop's
+  // sync, before the check of the slots, so the post-timing verify is outside.
+  // Empty (the default): nothing changes.
+  std::function<void()> before_timing;
+  std::function<void()> after_timing;
 };
 
 // One timed delivery the inline check found wrong (RunConfig::inline_check).
@@ -104,6 +112,19 @@ struct FlowResult {
   uint64_t checksum = 0;
 };
 
+// What a background load did beside one phase (RunConfig's hooks, --load).
+struct PhaseLoad {
+  bool present = false;
+  double quiet_agg_gbs = 0;  // the quiet pass's agg_gbs of this phase
+  // LoadStats summed over the ranks that ran a load (window_s: the longest;
+  // during_rate: their mean, per GPU like alone_rate; covered: all of them).
+  long launches = 0, launches_done = 0, window_launches = 0;
+  double window_s = 0;
+  double during_rate = 0;
+  bool covered = true;
+  std::vector<int> ranks;
+};
+
 struct PhaseResult {
   size_t index = 0;
   std::string label;
@@ -113,6 +134,10 @@ struct PhaseResult {
   int iters = 0;
   double seconds_per_iter = 0;  // phase time per iteration (max over participants)
   double wall_seconds = 0;      // host barrier-to-barrier time of the timed region
+  // This rank's host seconds between the two RunConfig hooks: warm-up, its
+  // check and the timed loop (what a background load has to cover).
+  double hooked_seconds = 0;
+  PhaseLoad load;               // --load: the loaded pass only
   double bytes_per_iter = 0;    // all flows of the phase
   double agg_gbs = 0;           // bytes_per_iter / seconds_per_iter
   std::vector<double> rank_seconds;  // each rank's own timed duration (0 = not participating)

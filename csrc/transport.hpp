@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "background_load.hpp"
 #include "diagnose.hpp"
 #include "prng.hpp"
 
@@ -240,6 +241,13 @@ class Transport {
   // ("P2P", "SHM", "NET", "self"; "" unknown or not connected); empty where
   // the transport has no such notion.
   virtual std::vector<std::string> peer_transports() { return {}; }
+
+  // ---- background load (--load) ----
+  // A load generator on this rank's GPU (background_load.hpp): `kind` "mfma"
+  // or "hbm", `wgs` workgroups per launch (0: one per CU), on a stream of its
+  // own, its waits bounded like sync().  Null where there is no GPU to load
+  // (the CPU transports).  It must be destroyed before the transport.
+  virtual std::unique_ptr<BackgroundLoad> make_load(const std::string& /*kind*/, int /*wgs*/) { return nullptr; }
 
   // ---- health ----
   // Non-empty when the transport saw an asynchronous error (e.g. a peer died).

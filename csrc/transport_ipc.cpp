@@ -59,6 +59,7 @@
 #include "device_checks.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
+#include "load.hpp"
 #include "provenance.hpp"
 #include "routing.hpp"
 #include "stream_gate.hpp"
@@ -567,6 +568,10 @@ class IpcTransport final : public Transport {
     return finish_ping(leader, laps, 1.0, strfmt("ring token (from %d, to %d)", pred, succ));
   }
 
+  std::unique_ptr<BackgroundLoad> make_load(const std::string& kind, int wgs) override {
+    HIPCHECK(hipSetDevice(device_));
+    return make_background_load(kind, wgs, timeout_, stream_);
+  }
   void set_timeout(double seconds) override { timeout_ = seconds; }
 
   void sync() override {

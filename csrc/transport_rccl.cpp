@@ -65,6 +65,7 @@
 #include "device_checks.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
+#include "load.hpp"
 #include "provenance.hpp"
 #include "rccl_log.hpp"
 #include "report.hpp"
@@ -494,6 +495,10 @@ class RcclTransport final : public Transport {
   }
   void gate_release() override { gate_.release(); }
   bool gate_timed_out() override { return gate_.timed_out(); }
+  std::unique_ptr<BackgroundLoad> make_load(const std::string& kind, int wgs) override {
+    HIPCHECK(hipSetDevice(device_));
+    return make_background_load(kind, wgs, timeout_, stream_);
+  }
   void set_timeout(double seconds) override { timeout_ = seconds; }
 
   std::string async_error() override {
