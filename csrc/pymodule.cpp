@@ -209,6 +209,15 @@ class Session {
     return strfmt("{\"supported\":true,\"timed_out\":%s,\"seconds\":%.4f}", expired ? "true" : "false", waited);
   }
 
+  // Test hooks for the rendezvous tests: the gate on its own (a rank holds
+  // its stream while its peers post), and whether the stream has finished
+  // what was posted, without waiting for it.
+  bool gate_arm(double timeout_s) { return t_->gate_arm(timeout_s); }
+  void gate_release() { t_->gate_release(); }
+  bool gate_timed_out() { return t_->gate_timed_out(); }
+  bool stream_idle() { return t_->stream_idle(); }
+  std::string async_error() { return t_->async_error(); }
+
   std::string device_latency(size_t bytes, int iters, int warmup) {
     return latency_to_json(run_device_latency(*t_, *boot_, bytes, iters, warmup), world());
   }
@@ -803,7 +812,17 @@ PYBIND11_MODULE(_p2pcore, m) {
            py::call_guard<NativeCall, py::gil_scoped_release>(),
            "Test hook: milliseconds between two marks of the transport; valid after a sync.")
       .def("_clear_marks", &Session::clear_marks, py::call_guard<NativeCall, py::gil_scoped_release>(),
-           "Test hook: forget the transport's marks (their ids are handed out again).");
+           "Test hook: forget the transport's marks (their ids are handed out again).")
+      .def("_gate_arm", &Session::gate_arm, py::arg("timeout_s"), py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: hold the transport's stream until _gate_release() or `timeout_s`; False where there is no gate.")
+      .def("_gate_release", &Session::gate_release, py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: let every armed gate pass.")
+      .def("_gate_timed_out", &Session::gate_timed_out, py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: did a gate expire instead of being released? Call it after a sync.")
+      .def("_stream_idle", &Session::stream_idle, py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: has the transport's stream finished everything posted so far? Never waits.")
+      .def("_async_error", &Session::async_error, py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Test hook: the transport's asynchronous error, '' when there is none.");
 
   py::class_<PyStepDriver>(m, "StepDriver")
       .def(py::init<std::shared_ptr<Session>, const std::string&, const std::string&, size_t, int, bool, bool, bool, int,
@@ -859,6 +878,8 @@ PYBIND11_MODULE(_p2pcore, m) {
           }, py::arg("step"),
            "This rank's receive slots of step `step`, in message order: [(address, bytes, sender, message)] "
            "(read them after sync()).")
+      .def("msg_seed", [](PyStepDriver& s, int src, int msg) { return s.d().msg_seed(src, msg); }, py::arg("src"),
+           py::arg("msg"), "PRNG stream of message `msg` as rank `src` sends it (what a delivery must hold).")
       .def("bytes_sent_per_step", [](PyStepDriver& s, long k) { return s.d().bytes_sent_per_step(k); })
       .def("job_bytes_per_step", [](PyStepDriver& s, long k) { return s.d().job_bytes_per_step(k); })
       .def_property_readonly("phases", [](PyStepDriver& s) { return s.d().phases(); })

@@ -820,11 +820,15 @@ std::vector<PhaseResult> run_schedule(Transport& t, Bootstrap& boot, const Sched
 void warm_connections(Transport& t, Bootstrap& boot, const Schedule& s, Buffers& bufs, size_t bytes) {
   bytes = std::min(bytes, bufs.capacity());
   for (const Phase& p : s.phases) {
-    if (!posts_phase(t, p, t.rank())) continue;
-    post_phase_iteration(t, p, bytes, bufs);
-    t.sync();
+    if (posts_phase(t, p, t.rank())) {
+      post_phase_iteration(t, p, bytes, bufs);
+      t.sync();
+    }
+    // The phases share receive slots, and the next phase's sender into a slot
+    // may be another rank: a push receiver's ready flag carries no release, so
+    // only the host orders the two writers (docs/DESIGN.md, slot reuse).
+    boot.barrier();
   }
-  boot.barrier();
 }
 
 // -------------------------------------------------------------- latency ----

@@ -215,6 +215,11 @@ class Transport {
   virtual bool gate_arm(double /*timeout_s*/) { return false; }
   virtual void gate_release() {}
   virtual bool gate_timed_out() { return false; }
+  // Non-blocking: true when everything posted so far has finished on the
+  // stream that carries the messages (GPU transports: hipStreamQuery).  Host
+  // transports finish inside their calls and are always idle.  Tests use it
+  // to see a stream parked in a rendezvous without waiting on it.
+  virtual bool stream_idle() { return true; }
 
   // ---- message chunking (RCCL) ----
   // Largest single op a message to a peer is posted as (0 = unsplit): the

@@ -21,7 +21,9 @@
 //            and a second signal kernel releases it and raises "done" on the
 //            receiver, whose stream waits for that.  Real send/recv semantics
 //            (a send never overwrites a slot the receiver has not posted) on
-//            the direction xGMI handles best (remote stores).
+//            the direction xGMI handles best (remote stores).  Which flags,
+//            values and launches: PushPlanner (push_plan.hpp), for push and
+//            relay alike; this file maps them to addresses and launches.
 //   relay  — push, multi-path: each message is split into stripes
 //            (routing.hpp plan_routes), one over the direct link, written by
 //            the sender, and one per two-hop path s -> k -> d through a GPU k
@@ -61,6 +63,7 @@
 #include "kernels.hpp"
 #include "load.hpp"
 #include "provenance.hpp"
+#include "push_plan.hpp"
 #include "routing.hpp"
 #include "stream_gate.hpp"
 #include "transport.hpp"
@@ -85,7 +88,7 @@ class IpcTransport final : public Transport {
         checks_(static_cast<dev::VerifyImpl>(opt.verify_impl)) {
     P2P_CHECK(engine_ == "kernel" || engine_ == "sdma" || engine_ == "push" || relay_,
               "ipc engine must be 'kernel', 'sdma', 'push' or 'relay'");
-    if (relay_) route_opt_ = route_options_from_env();
+    static_assert(kPushMaxSignals == dev::kMaxSignals, "the planner cuts signals to what one launch carries");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) P2P_FATAL("ipc transport: no HIP device visible");
     device_ = opt.device >= 0 ? opt.device : 0;
@@ -108,7 +111,10 @@ class IpcTransport final : public Transport {
     if (hipRuntimeGetVersion(&hip_rt) != hipSuccess) hip_rt = 0;
     size_fix_ = hip_rt < 70200000;
     if (const char* sf = std::getenv("P2P_IPC_SIZE_FIX")) size_fix_ = std::atoi(sf) != 0;
-    if (push_) setup_sync_pages();
+    if (push_) {
+      plan_ = std::make_unique<PushPlanner>(rank_, n_, relay_, relay_ ? route_options_from_env() : RouteOptions());
+      setup_sync_pages();
+    }
   }
 
   ~IpcTransport() override {
@@ -284,7 +290,7 @@ class IpcTransport final : public Transport {
     in_group_ = true;
     ops_.clear();
     checked_ops_.clear();
-    covered_.clear();
+    if (plan_) plan_->group_begin();
   }
 
   bool wants_group_flows() const override { return relay_; }
@@ -300,29 +306,14 @@ class IpcTransport final : public Transport {
     for (const auto& r : regs_)
       if (r.send == set_send) reg = &r;
     P2P_CHECK(reg && bytes <= reg->slot_bytes, "ipc relay: flows of an unregistered buffer set");
-    std::vector<std::pair<int, int>> pairs;
-    pairs.reserve(flows.size());
-    for (const auto& f : flows) pairs.emplace_back(f.src, f.dst);
-    const auto plan = plan_routes(n_, pairs, bytes, route_opt_);
-    for (size_t i = 0; i < flows.size(); ++i) {
-      const GroupFlow& f = flows[i];
-      if (f.src == f.dst) continue;  // self flows: the endpoint's send / recv copy locally
-      P2P_CHECK(f.src_offset + bytes <= reg->send_bytes, "ipc relay: message outside the send buffer");
-      char* slot = remote_slot_ptr(*reg, f.dst, f.slot);
-      for (const Stripe& st : plan[i]) {
-        const int writer = st.via < 0 ? f.src : st.via;
-        if (rank_ == writer) {
-          const char* src = static_cast<const char*>(reg->peer_send[static_cast<size_t>(f.src)]) + f.src_offset;
-          if (!discarding()) ops_.push_back({src + st.offset, slot + st.offset, st.bytes, true});
-          push_sends_.push_back(f.dst);  // wait for its ready, raise its done
-          if (st.via >= 0) {
-            relayed_bytes_ += st.bytes;
-            ++relayed_stripes_;
-          }
-        }
-        if (rank_ == f.dst) push_recvs_.push_back(writer);  // post ready, wait for done
+    for (const auto& f : flows)
+      P2P_CHECK(f.src == f.dst || f.src_offset + bytes <= reg->send_bytes, "ipc relay: message outside the send buffer");
+    for (const PushCopy& c : plan_->group_flows(flows, bytes, discarding())) {
+      push_copy(*reg, c);
+      if (c.src != rank_) {
+        relayed_bytes_ += c.bytes;
+        ++relayed_stripes_;
       }
-      if (rank_ == f.src || rank_ == f.dst) covered_.push_back({f.src, f.dst, f.slot});
     }
   }
 
@@ -336,11 +327,10 @@ class IpcTransport final : public Transport {
         reg = &r;
     P2P_CHECK(reg, "ipc transport sends only from a registered send buffer");
     if (!push_) return;  // nothing to move: the receiver pulls
-    if (take_covered(rank_, peer, slot)) return;  // posted by group_flows
-    char* dst = remote_slot_ptr(*reg, peer, slot);
     // Injected skip fault: the rendezvous runs, the payload stays behind.
-    if (!discarding()) ops_.push_back({p, dst, bytes, peer != rank_});
-    if (peer != rank_) push_sends_.push_back(peer);
+    PushCopy c;
+    const size_t src_offset = static_cast<size_t>(static_cast<const char*>(p) - static_cast<const char*>(reg->send));
+    if (plan_->send(src_offset, bytes, peer, slot, discarding(), &c)) push_copy(*reg, c);
     if (!in_group_) flush();
   }
   void recv(void* p, size_t bytes, int peer) override { recv_from(p, bytes, peer, 0); }
@@ -382,8 +372,7 @@ class IpcTransport final : public Transport {
     }
     P2P_CHECK(reg, "ipc transport receives only into a registered receive slot");
     if (push_) {
-      if (take_covered(peer, rank_, slot)) return;  // posted by group_flows
-      if (peer != rank_) push_recvs_.push_back(peer);  // a self receive is the self send's copy
+      plan_->recv(peer, slot);
       if (!in_group_) flush();
       return;
     }
@@ -408,7 +397,7 @@ class IpcTransport final : public Transport {
   void group_end() override {
     P2P_CHECK(in_group_, "group_end without group_begin");
     in_group_ = false;
-    P2P_CHECK(covered_.empty(), "ipc relay: group_flows named a flow this rank did not post");
+    P2P_CHECK(!plan_ || plan_->group_complete(), "ipc relay: group_flows named a flow this rank did not post");
     flush();
   }
 
@@ -466,6 +455,11 @@ class IpcTransport final : public Transport {
   }
   void gate_release() override { gate_.release(); }
   bool gate_timed_out() override { return gate_.timed_out(); }
+  bool stream_idle() override {
+    const hipError_t e = hipStreamQuery(stream_);
+    if (e != hipSuccess && e != hipErrorNotReady) P2P_FATAL(strfmt("stream error: %s", hipGetErrorString(e)));
+    return e == hipSuccess;
+  }
   bool supports_device_pingpong() const override { return true; }
   void pingpong_setup() override {
     if (ping_ready_) return;  // same state on every rank: they all set up together
@@ -695,41 +689,33 @@ class IpcTransport final : public Transport {
     }
   }
 
-  // A flow (src, dst, slot) that group_flows already posted for this rank;
-  // consumed by the endpoint's matching send / recv call.
-  bool take_covered(int src, int dst, int slot) {
-    const std::array<int, 3> key{src, dst, slot};
-    auto it = std::find(covered_.begin(), covered_.end(), key);
-    if (it == covered_.end()) return false;
-    covered_.erase(it);
-    return true;
+  // A stripe the planner gave this rank, as a copy between mapped buffers.
+  void push_copy(const Registration& reg, const PushCopy& c) {
+    const char* src = static_cast<const char*>(reg.peer_send[static_cast<size_t>(c.src)]) + c.src_offset + c.offset;
+    char* dst = remote_slot_ptr(reg, c.dst, c.slot) + c.offset;
+    ops_.push_back({src, dst, c.bytes, c.src != rank_ || c.dst != rank_});
   }
 
-  // Push group: readies out / readies in, the copies, then done out / done in.
+  // Push group (push_plan.hpp): readies out / readies in, the copies, then
+  // done out / done in.
   void flush_push() {
-    dev::SignalArgs pre{}, post{};
-    for (int p : push_recvs_) add_post(&pre, p, kReady, ++ready_posted_[static_cast<size_t>(p)]);
-    for (int q : push_sends_) add_wait(&pre, q, kReady, ++ready_seen_[static_cast<size_t>(q)]);
+    const PushFlush f = plan_->flush();
     if (debug_) {
       std::string msg = strfmt("[ipc %d] group %ld sends-to:", rank_, groups_);
-      for (int q : push_sends_) msg += strfmt(" %d", q);
+      for (const auto& q : f.pre_waits) msg += strfmt(" %d", q.peer);
       msg += " recvs-from:";
-      for (int p : push_recvs_) msg += strfmt(" %d", p);
+      for (const auto& p : f.pre_posts) msg += strfmt(" %d", p.peer);
       msg += " ready_posted:";
-      for (auto v : ready_posted_) msg += strfmt(" %llu", v);
+      for (auto v : plan_->ready_posted()) msg += strfmt(" %llu", v);
       msg += " ready_seen:";
-      for (auto v : ready_seen_) msg += strfmt(" %llu", v);
+      for (auto v : plan_->ready_seen()) msg += strfmt(" %llu", v);
       std::fprintf(stderr, "%s ops %zu\n", msg.c_str(), ops_.size());
     }
     ++groups_;
-    launch_signals(pre, false);
+    for (const PushPiece& piece : f.pre) launch_signals(piece);
     if (!ops_.empty()) dev::launch_multi_copy(ops_.data(), static_cast<int>(ops_.size()), stream_);
-    for (int q : push_sends_) add_post(&post, q, kDone, ++done_posted_[static_cast<size_t>(q)]);
-    for (int p : push_recvs_) add_wait(&post, p, kDone, ++done_seen_[static_cast<size_t>(p)]);
-    launch_signals(post, true);
+    for (const PushPiece& piece : f.post) launch_signals(piece);
     ops_.clear();
-    push_sends_.clear();
-    push_recvs_.clear();
   }
 
   // Signal page line of kind k (ready / done) that rank `from` writes.
@@ -737,34 +723,23 @@ class IpcTransport final : public Transport {
     return reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(page) +
                                                  kSyncLine * (static_cast<size_t>(kind) * n_ + static_cast<size_t>(from)));
   }
-  // Several messages to one peer in a group share its flag: keep one entry
-  // per flag with the highest value (lanes storing to one address at once
-  // would leave an arbitrary one of the values).
-  void add_post(dev::SignalArgs* a, int peer, int kind, unsigned long long v) {
-    unsigned long long* f = sync_line(sync_peer_[static_cast<size_t>(peer)], kind, rank_);
-    for (int i = 0; i < a->nposts; ++i)
-      if (a->post_flag[i] == f) {
-        a->post_value[i] = std::max(a->post_value[i], v);
-        return;
-      }
-    if (a->nposts == dev::kMaxSignals) launch_signals(*a, false), *a = dev::SignalArgs{};
-    a->post_flag[a->nposts] = f;
-    a->post_value[a->nposts++] = v;
-  }
-  void add_wait(dev::SignalArgs* a, int peer, int kind, unsigned long long v) {
-    const unsigned long long* f = sync_line(sync_page_, kind, peer);
-    for (int i = 0; i < a->nwaits; ++i)
-      if (a->wait_flag[i] == f) {
-        a->wait_value[i] = std::max(a->wait_value[i], v);
-        return;
-      }
-    if (a->nwaits == dev::kMaxSignals) launch_signals(*a, false), *a = dev::SignalArgs{};
-    a->wait_flag[a->nwaits] = f;
-    a->wait_value[a->nwaits++] = v;
-  }
-  void launch_signals(dev::SignalArgs a, bool release_first) {
-    if (a.nposts == 0 && a.nwaits == 0) return;
-    a.release_first = release_first ? 1 : 0;
+  // A post goes to this rank's line in the peer's page, a wait reads the
+  // peer's line in this rank's page.
+  void launch_signals(const PushPiece& piece) {
+    if (piece.posts.empty() && piece.waits.empty()) return;
+    P2P_CHECK(piece.posts.size() <= static_cast<size_t>(dev::kMaxSignals) &&
+                  piece.waits.size() <= static_cast<size_t>(dev::kMaxSignals),
+              "ipc push: a signal piece larger than one launch");
+    dev::SignalArgs a{};
+    for (const PushFlag& f : piece.posts) {
+      a.post_flag[a.nposts] = sync_line(sync_peer_[static_cast<size_t>(f.peer)], f.kind, rank_);
+      a.post_value[a.nposts++] = f.value;
+    }
+    for (const PushFlag& f : piece.waits) {
+      a.wait_flag[a.nwaits] = sync_line(sync_page_, f.kind, f.peer);
+      a.wait_value[a.nwaits++] = f.value;
+    }
+    a.release_first = piece.release_first ? 1 : 0;
     a.status = sig_status_;
     a.timeout_ticks = static_cast<unsigned long long>(timeout_ * tick_hz_);
     dev::launch_signal(a, stream_);
@@ -815,7 +790,6 @@ class IpcTransport final : public Transport {
       HIPCHECK(hipIpcOpenMemHandle(&mapped, all[static_cast<size_t>(r)].handle, hipIpcMemLazyEnablePeerAccess));
       sync_peer_[static_cast<size_t>(r)] = mapped;
     }
-    for (auto* v : {&ready_posted_, &ready_seen_, &done_posted_, &done_seen_}) v->assign(static_cast<size_t>(n_), 0);
     boot_.barrier();
   }
 
@@ -883,7 +857,6 @@ class IpcTransport final : public Transport {
   std::string engine_;
   bool relay_;  // multi-path push (engine "relay")
   bool push_;   // rendezvous + remote writes (engines "push" and "relay")
-  RouteOptions route_opt_;
   int device_ = 0;
   hipStream_t stream_ = nullptr;
   StreamGate gate_;
@@ -900,7 +873,6 @@ class IpcTransport final : public Transport {
   std::vector<dev::CopyOp> ops_;
   std::vector<dev::CheckedCopyOp> checked_ops_;  // kernel engine: receives checked as they are copied
   bool capturing_ = false;
-  std::vector<std::array<int, 3>> covered_;  // relay: (src, dst, slot) posted by group_flows
   unsigned long long relayed_bytes_ = 0, relayed_stripes_ = 0;  // moved by this rank as a relay (P2P_RELAY_STATS)
   bool debug_ = std::getenv("P2P_IPC_DEBUG") != nullptr;     // per-group flag bookkeeping on stderr
   long groups_ = 0;
@@ -963,12 +935,10 @@ class IpcTransport final : public Transport {
 
   // Push / relay engine state.
   static constexpr size_t kSyncLine = 128;
-  static constexpr int kReady = 0, kDone = 1;
   void* sync_page_ = nullptr;
   std::vector<void*> sync_peer_;
   unsigned int* sig_status_ = nullptr;  // host-mapped; bit 0 = a signal wait timed out
-  std::vector<unsigned long long> ready_posted_, ready_seen_, done_posted_, done_seen_;
-  std::vector<int> push_sends_, push_recvs_;  // peers this rank writes to / receives from in the group
+  std::unique_ptr<PushPlanner> plan_;  // flag counters and every post / wait decision (push_plan.hpp)
 
   static constexpr size_t kPingHeader = 256;            // flag + padding (own cache lines)
   static constexpr size_t kPingMaxBytes = 64u << 10;

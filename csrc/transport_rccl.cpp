@@ -495,6 +495,11 @@ class RcclTransport final : public Transport {
   }
   void gate_release() override { gate_.release(); }
   bool gate_timed_out() override { return gate_.timed_out(); }
+  bool stream_idle() override {
+    const hipError_t e = hipStreamQuery(stream_);
+    if (e != hipSuccess && e != hipErrorNotReady) P2P_FATAL(strfmt("stream error: %s", hipGetErrorString(e)));
+    return e == hipSuccess;
+  }
   std::unique_ptr<BackgroundLoad> make_load(const std::string& kind, int wgs) override {
     HIPCHECK(hipSetDevice(device_));
     return make_background_load(kind, wgs, timeout_, stream_);

@@ -23,6 +23,7 @@
 #include "bootstrap.hpp"
 #include "common.hpp"
 #include "prng.hpp"
+#include "push_plan.hpp"
 #include "rccl_log.hpp"
 #include "report.hpp"
 #include "routing.hpp"
@@ -1857,6 +1858,757 @@ TEST(test_abort_if_idle_waits_for_native_calls) {
   EXPECT(refused);
   EXPECT(abort_if_idle() && ran == 1);  // the hooks ran once
 }
+
+// ------------------- push / relay rendezvous: recorded programs vs a model ----
+//
+// T0r.  The IPC push and relay engines promise that no byte is written into a
+// receive slot before its receiver said it is ready, and that a receive
+// completes on the stream only once every writer's bytes are there.  Which
+// flags a rank posts and waits for, with which values, in which order around
+// its copies, is decided by PushPlanner (push_plan.hpp).  Here the real runner
+// drives one planner per rank, exactly as IpcTransport does, over the host
+// transport (which moves the bytes, so the runner's own verification runs);
+// what each rank would have put on its stream is recorded as a program, and
+// the N programs are evaluated in a model written from the contract:
+//   * a flag belongs to (owner rank, kind, posting rank) and only grows;
+//   * a rank's stream runs its program in order; the host posts it in order,
+//     sync() waits for the stream, a collective of the control plane (barrier,
+//     all-gather) orders what every rank's host knew before it against what
+//     any rank posts after it;
+//   * a signal issues all its posts, then waits for all its waits;
+//   * a wait (flag, v) is enabled by the first post that brings the flag to
+//     >= v, and learns from it: only that the post was issued, unless the
+//     post's signal released first -- then everything that happened before
+//     the signal on the poster's stream.
+// Happens-before is tracked with two prefixes per rank: `strong[r] = k`, the
+// first k operations of r's program have completed and are visible, and
+// `weak[r] = k`, the signals among them have issued their posts.
+//
+// Deliberately not a property: a relay reads the sender's send buffer without
+// telling the sender when it is finished (a writer raises `done` at the
+// receiver only).  The runner rewrites send regions only between barriers, so
+// the model does not ask for an edge from a relay's copy back to the sender.
+
+struct RvOp {
+  enum Kind { Signal, Copy, Sync, Collective } kind = Signal;
+  long group = -1;  // rank-local group the operation belongs to (Signal, Copy)
+  // Signal
+  std::vector<PushFlag> posts, waits;
+  bool release_first = false;
+  bool after_copies = false;
+  // Copy
+  PushCopy copy;
+  long seq = -1;  // which message (src, dst, slot) of the run it belongs to
+};
+
+struct RvRecv {  // a message as its receiver posted it
+  long group = -1;
+  int src = -1, slot = 0;
+  size_t bytes = 0, src_offset = 0;
+  long seq = -1;
+  bool payload = true;  // false: posted under an injected skip fault (every rank's, in these tests)
+};
+
+struct RvProgram {
+  std::vector<RvOp> ops;
+  std::vector<RvRecv> recvs;
+};
+
+class RendezvousRecorder final : public Transport {
+ public:
+  RendezvousRecorder(Transport& t, bool relay, int max_signals)
+      : t_(&t), plan_(t.rank(), t.nranks(), relay, RouteOptions(), max_signals) {}
+  std::string name() const override { return "rendezvous-recorder"; }
+  int rank() const override { return t_->rank(); }
+  int nranks() const override { return t_->nranks(); }
+  void* alloc(size_t b) override { return t_->alloc(b); }
+  void release(void* p) override { t_->release(p); }
+  void fill(void* p, size_t b, uint64_t s) override { t_->fill(p, b, s); }
+  void zero(void* p, size_t b) override { t_->zero(p, b); }
+  VerifyResult verify(const void* p, size_t b, uint64_t s) override { return t_->verify(p, b, s); }
+  int mark() override { return t_->mark(); }
+  double elapsed_ms(int a, int b) override { return t_->elapsed_ms(a, b); }
+  void clear_marks() override { t_->clear_marks(); }
+  void register_buffers(const BufferSet& set) override {
+    sets_.push_back(set);
+    t_->register_buffers(set);
+  }
+  void unregister_buffers(void* send) override {
+    sets_.erase(std::remove_if(sets_.begin(), sets_.end(), [&](const BufferSet& s) { return s.send == send; }), sets_.end());
+    t_->unregister_buffers(send);
+  }
+  void sync() override {
+    t_->sync();
+    RvOp op;
+    op.kind = RvOp::Sync;
+    prog.ops.push_back(op);
+  }
+  void note_collective() {
+    RvOp op;
+    op.kind = RvOp::Collective;
+    prog.ops.push_back(op);
+  }
+
+  void group_begin() override {
+    EXPECT(!in_group_);
+    in_group_ = true;
+    plan_.group_begin();
+    t_->group_begin();
+  }
+  bool wants_group_flows() const override { return plan_.relay(); }
+  void group_flows(const void*, const std::vector<GroupFlow>& flows, size_t bytes) override {
+    EXPECT(in_group_);
+    for (const auto& f : flows)
+      if (f.src != f.dst) message(f.src, f.dst, f.slot);
+    for (const PushCopy& c : plan_.group_flows(flows, bytes, discarding())) add_copy(c);
+  }
+  void send(const void* p, size_t b, int peer) override { send_to_slot(p, b, peer, 0); }
+  void send_to_slot(const void* p, size_t bytes, int peer, int slot) override {
+    const BufferSet* set = nullptr;
+    for (const auto& s : sets_)
+      if (p >= s.send && static_cast<const char*>(p) + bytes <= static_cast<const char*>(s.send) + s.send_bytes) set = &s;
+    EXPECT(set != nullptr);
+    if (!set) return;
+    message(rank(), peer, slot);
+    PushCopy c;
+    if (plan_.send(static_cast<size_t>(static_cast<const char*>(p) - static_cast<const char*>(set->send)), bytes, peer, slot,
+                   discarding(), &c))
+      add_copy(c);
+    t_->send(p, bytes, peer);
+    if (!in_group_) flush();
+  }
+  void recv(void* p, size_t b, int peer) override { recv_from(p, b, peer, 0); }
+  void recv_from(void* p, size_t bytes, int peer, size_t src_offset) override {
+    int slot = -1;
+    for (const auto& s : sets_) {
+      const char* base = static_cast<const char*>(s.recv);
+      const char* q = static_cast<const char*>(p);
+      if (q >= base && q < base + s.stride * static_cast<size_t>(s.nslots) && static_cast<size_t>(q - base) % s.stride == 0)
+        slot = static_cast<int>(static_cast<size_t>(q - base) / s.stride);
+    }
+    EXPECT(slot >= 0);
+    if (slot < 0) return;
+    prog.recvs.push_back({group_, peer, slot, bytes, src_offset, message(peer, rank(), slot), !discarding()});
+    plan_.recv(peer, slot);
+    t_->recv(p, bytes, peer);
+    if (!in_group_) flush();
+  }
+  void group_end() override {
+    EXPECT(in_group_);
+    in_group_ = false;
+    EXPECT(plan_.group_complete());
+    flush();
+    t_->group_end();
+  }
+
+  RvProgram prog;
+
+ private:
+  // The ordinal of the message (src, dst, slot) among those this rank has
+  // seen between the two ranks and that slot; one message per group and key,
+  // whichever of group_flows / send / recv names it first.
+  long message(int src, int dst, int slot) {
+    const std::array<int, 3> key{src, dst, slot};
+    auto it = in_group_seq_.find(key);
+    if (it != in_group_seq_.end()) return it->second;
+    const long seq = count_[key]++;
+    in_group_seq_[key] = seq;
+    return seq;
+  }
+  void add_copy(const PushCopy& c) {
+    RvOp op;
+    op.kind = RvOp::Copy;
+    op.copy = c;
+    op.seq = message(c.src, c.dst, c.slot);
+    copies_.push_back(op);
+  }
+  // What IpcTransport::flush_push puts on the stream, in its order.
+  void flush() {
+    const PushFlush f = plan_.flush();
+    auto signals = [&](const std::vector<PushPiece>& pieces, bool after) {
+      for (const PushPiece& piece : pieces) {
+        RvOp op;
+        op.kind = RvOp::Signal;
+        op.group = group_;
+        op.posts = piece.posts;
+        op.waits = piece.waits;
+        op.release_first = piece.release_first;
+        op.after_copies = after;
+        prog.ops.push_back(op);
+      }
+    };
+    signals(f.pre, false);
+    for (RvOp& c : copies_) {
+      c.group = group_;
+      prog.ops.push_back(c);
+    }
+    signals(f.post, true);
+    copies_.clear();
+    in_group_seq_.clear();
+    ++group_;
+  }
+
+  Transport* t_;
+  PushPlanner plan_;
+  std::vector<BufferSet> sets_;
+  bool in_group_ = false;
+  long group_ = 0;
+  std::vector<RvOp> copies_;
+  std::map<std::array<int, 3>, long> count_, in_group_seq_;
+};
+
+// The control plane with its collectives noted in the rank's program.
+class CollectiveRecorder final : public Bootstrap {
+ public:
+  CollectiveRecorder(Bootstrap& b, RendezvousRecorder& rec) : b_(&b), rec_(&rec) {}
+  int rank() const override { return b_->rank(); }
+  int size() const override { return b_->size(); }
+  void allgather(const void* mine, void* all, size_t bytes) override {
+    rec_->note_collective();
+    b_->allgather(mine, all, bytes);
+  }
+  void bcast(void* buf, size_t bytes, int root) override { b_->bcast(buf, bytes, root); }
+  void barrier() override {
+    rec_->note_collective();
+    b_->barrier();
+  }
+  void abort(int code) override { b_->abort(code); }
+  std::string name() const override { return b_->name(); }
+  void set_timeout(double s) override { b_->set_timeout(s); }
+
+ private:
+  Bootstrap* b_;
+  RendezvousRecorder* rec_;
+};
+
+struct RvClock {
+  std::vector<long> strong, weak;
+  explicit RvClock(int n = 0) : strong(static_cast<size_t>(n), 0), weak(static_cast<size_t>(n), 0) {}
+  void join(const RvClock& o) {
+    for (size_t i = 0; i < strong.size(); ++i) {
+      strong[i] = std::max(strong[i], o.strong[i]);
+      weak[i] = std::max(weak[i], o.weak[i]);
+    }
+  }
+};
+
+// Evaluates the programs; returns what the contract forbids, one line each
+// ("liveness: ...", "ready: ...", "done: ...", "reuse: ...", "tiling: ...",
+// "balance: ...", "monotone: ...").
+static std::vector<std::string> rendezvous_violations(const std::vector<RvProgram>& progs) {
+  std::vector<std::string> bad;
+  const int n = static_cast<int>(progs.size());
+  struct Post {
+    unsigned long long value;
+    RvClock carried;
+  };
+  std::map<std::array<int, 3>, std::vector<Post>> flags;         // (owner, kind, poster) -> posts in order
+  std::map<std::array<int, 3>, unsigned long long> most_waited;  // the same key -> highest value waited for
+  struct Rank {
+    size_t hp = 0, sp = 0;   // next operation of the host / of the stream
+    bool posted = false;     // the signal at sp has issued its posts
+    RvClock host, stream;
+    std::vector<RvClock> posted_at;  // per operation: what the host knew when it posted it
+    std::vector<RvClock> at;         // per operation: Copy: when it ran; Signal: when it ended
+  };
+  std::vector<Rank> st(static_cast<size_t>(n));
+  for (int r = 0; r < n; ++r) {
+    Rank& k = st[static_cast<size_t>(r)];
+    k.host = k.stream = RvClock(n);
+    k.posted_at.assign(progs[static_cast<size_t>(r)].ops.size(), RvClock());
+    k.at.assign(progs[static_cast<size_t>(r)].ops.size(), RvClock());
+  }
+  auto on_stream = [](const RvOp& op) { return op.kind == RvOp::Signal || op.kind == RvOp::Copy; };
+  for (bool progress = true; progress;) {
+    progress = false;
+    for (int r = 0; r < n; ++r) {
+      Rank& k = st[static_cast<size_t>(r)];
+      const auto& ops = progs[static_cast<size_t>(r)].ops;
+      // The host: posts stream work without waiting, waits at a sync.
+      while (k.hp < ops.size()) {
+        const RvOp& op = ops[k.hp];
+        if (on_stream(op)) {
+          k.posted_at[k.hp] = k.host;
+        } else if (op.kind == RvOp::Sync) {
+          if (k.sp < k.hp) break;
+          k.host.join(k.stream);
+        } else {
+          break;  // a collective: below, once every rank is at one
+        }
+        ++k.hp;
+        progress = true;
+      }
+      // The stream: what was posted, in order.
+      while (k.sp < k.hp) {
+        const RvOp& op = ops[k.sp];
+        const size_t i = k.sp;
+        if (!on_stream(op)) {
+          ++k.sp;
+          progress = true;
+          continue;
+        }
+        if (op.kind == RvOp::Copy) {
+          k.stream.join(k.posted_at[i]);
+          k.at[i] = k.stream;
+        } else {
+          if (!k.posted) {
+            k.stream.join(k.posted_at[i]);
+            RvClock carried(n);
+            if (op.release_first) carried = k.stream;
+            carried.weak[static_cast<size_t>(r)] = static_cast<long>(i) + 1;
+            for (const PushFlag& f : op.posts) {
+              auto& line = flags[{f.peer, f.kind, r}];
+              if (!line.empty() && line.back().value >= f.value)
+                bad.push_back(strfmt("monotone: rank %d posts %llu on a flag that holds %llu", r, f.value, line.back().value));
+              line.push_back({f.value, carried});
+            }
+            k.posted = true;
+            progress = true;
+          }
+          bool open = true;
+          for (const PushFlag& f : op.waits) {
+            const auto& line = flags[{r, f.kind, f.peer}];
+            open = open && !line.empty() && line.back().value >= f.value;
+          }
+          if (!open) break;
+          for (const PushFlag& f : op.waits) {
+            const auto& line = flags[{r, f.kind, f.peer}];
+            for (const Post& p : line)
+              if (p.value >= f.value) {
+                k.stream.join(p.carried);
+                break;
+              }
+            auto& w = most_waited[{r, f.kind, f.peer}];
+            w = std::max(w, f.value);
+          }
+          k.posted = false;
+          k.stream.weak[static_cast<size_t>(r)] = static_cast<long>(i) + 1;
+          k.at[i] = k.stream;
+        }
+        k.stream.strong[static_cast<size_t>(r)] = static_cast<long>(i) + 1;
+        if (op.kind == RvOp::Signal) k.at[i].strong[static_cast<size_t>(r)] = static_cast<long>(i) + 1;
+        ++k.sp;
+        progress = true;
+      }
+    }
+    // A collective completes once every rank's host has reached it.
+    bool all = true;
+    for (int r = 0; r < n; ++r) {
+      const Rank& k = st[static_cast<size_t>(r)];
+      const auto& ops = progs[static_cast<size_t>(r)].ops;
+      all = all && k.hp < ops.size() && ops[k.hp].kind == RvOp::Collective;
+    }
+    if (all) {
+      RvClock joined(n);
+      for (const Rank& k : st) joined.join(k.host);
+      for (Rank& k : st) {
+        k.host = joined;
+        ++k.hp;
+      }
+      progress = true;
+    }
+  }
+  for (int r = 0; r < n; ++r) {
+    const Rank& k = st[static_cast<size_t>(r)];
+    const auto& ops = progs[static_cast<size_t>(r)].ops;
+    if (k.hp == ops.size() && k.sp == ops.size()) continue;
+    std::string what = k.sp < ops.size() && ops[k.sp].kind == RvOp::Signal ? "a signal that waits for" : "operation";
+    if (k.sp < ops.size() && ops[k.sp].kind == RvOp::Signal)
+      for (const PushFlag& f : ops[k.sp].waits) what += strfmt(" (%d,%s,%llu)", f.peer, f.kind == kPushReady ? "ready" : "done", f.value);
+    bad.push_back(strfmt("liveness: rank %d stops at %zu of %zu (host at %zu): %s", r, k.sp, ops.size(), k.hp, what.c_str()));
+  }
+  if (!bad.empty()) return bad;  // the orders below are those of a finished run
+
+  // Balance: what was posted last on a flag is what was last waited for.
+  for (const auto& kv : flags)
+    if (!kv.second.empty() && kv.second.back().value != most_waited[kv.first])
+      bad.push_back(strfmt("balance: flag (%d,%d,%d) was posted up to %llu and waited for up to %llu", kv.first[0], kv.first[1],
+                           kv.first[2], kv.second.back().value, most_waited[kv.first]));
+  for (const auto& kv : most_waited)
+    if (flags[kv.first].empty()) bad.push_back(strfmt("balance: flag (%d,%d,%d) is waited for and never posted", kv.first[0], kv.first[1], kv.first[2]));
+
+  // Every copy, by the message it belongs to.
+  struct Written {
+    int writer;
+    size_t index;
+    const RvOp* op;
+  };
+  std::map<std::array<long, 4>, std::vector<Written>> by_message;  // (src, dst, slot, seq)
+  size_t ncopies = 0;
+  for (int w = 0; w < n; ++w) {
+    const auto& ops = progs[static_cast<size_t>(w)].ops;
+    for (size_t i = 0; i < ops.size(); ++i)
+      if (ops[i].kind == RvOp::Copy) {
+        by_message[{ops[i].copy.src, ops[i].copy.dst, ops[i].copy.slot, ops[i].seq}].push_back({w, i, &ops[i]});
+        ++ncopies;
+      }
+  }
+  size_t matched = 0;
+  struct Landed {
+    long order;  // position of the message in the receiver's posting order
+    Written w;
+  };
+  std::map<std::array<int, 2>, std::vector<Landed>> by_slot;  // (dst, slot)
+  for (int d = 0; d < n; ++d) {
+    const RvProgram& prog = progs[static_cast<size_t>(d)];
+    for (size_t m = 0; m < prog.recvs.size(); ++m) {
+      const RvRecv& rv = prog.recvs[m];
+      auto found = by_message.find({rv.src, d, rv.slot, rv.seq});
+      std::vector<Written> parts = found == by_message.end() ? std::vector<Written>() : found->second;
+      matched += parts.size();
+      if (!rv.payload) {
+        if (!parts.empty()) bad.push_back(strfmt("tiling: %zu copies of a discarded message %d->%d", parts.size(), rv.src, d));
+        continue;
+      }
+      // Tiling: the parts cover [0, bytes) once, each from the same offset of
+      // the sender's message.
+      std::sort(parts.begin(), parts.end(), [](const Written& a, const Written& b) { return a.op->copy.offset < b.op->copy.offset; });
+      size_t end = 0;
+      bool tiles = true;
+      for (const Written& p : parts) {
+        tiles = tiles && p.op->copy.offset == end && p.op->copy.src_offset == rv.src_offset && p.op->copy.bytes > 0;
+        end += p.op->copy.bytes;
+      }
+      if (!tiles || end != rv.bytes)
+        bad.push_back(strfmt("tiling: message %d->%d slot %d #%ld of %zu bytes is covered up to %zu by %zu copies", rv.src, d,
+                             rv.slot, rv.seq, rv.bytes, end, parts.size()));
+      // The receiver's two signals of the group.
+      long last_post = -1;
+      for (size_t i = 0; i < prog.ops.size(); ++i)
+        if (prog.ops[i].kind == RvOp::Signal && prog.ops[i].group == rv.group && prog.ops[i].after_copies)
+          last_post = static_cast<long>(i);
+      for (const Written& p : parts) {
+        by_slot[{d, rv.slot}].push_back({static_cast<long>(m), p});
+        if (p.writer == d) {  // a self message: stream order, no rendezvous
+          if (p.op->group != rv.group) bad.push_back(strfmt("ready: self copy of rank %d outside its receive's group", d));
+          continue;
+        }
+        // Writer waits for ready: the copy knows of the receiver's signal
+        // that tells this writer so.
+        long ready_at = -1;
+        for (size_t i = 0; i < prog.ops.size(); ++i) {
+          const RvOp& op = prog.ops[i];
+          if (op.kind != RvOp::Signal || op.group != rv.group || op.after_copies) continue;
+          for (const PushFlag& f : op.posts)
+            if (f.peer == p.writer && f.kind == kPushReady) ready_at = static_cast<long>(i);
+        }
+        const RvClock& when = st[static_cast<size_t>(p.writer)].at[p.index];
+        if (ready_at < 0 || when.weak[static_cast<size_t>(d)] < ready_at + 1)
+          bad.push_back(strfmt("ready: rank %d writes %d->%d slot %d #%ld before rank %d said it is ready", p.writer, rv.src, d,
+                               rv.slot, rv.seq, d));
+        // Receive completes after the data: the end of the receiver's
+        // post-signal knows the copy, which only a releasing done gives it.
+        if (last_post < 0 || st[static_cast<size_t>(d)].at[static_cast<size_t>(last_post)].strong[static_cast<size_t>(p.writer)] <
+                                 static_cast<long>(p.index) + 1)
+          bad.push_back(strfmt("done: rank %d's receive of %d->%d slot %d #%ld completes without rank %d's copy", d, rv.src, d,
+                               rv.slot, rv.seq, p.writer));
+      }
+    }
+  }
+  if (matched != ncopies) bad.push_back(strfmt("tiling: %zu of %zu copies belong to no posted receive", ncopies - matched, ncopies));
+  // Slot reuse: copies into overlapping bytes of one slot are ordered like
+  // the receiver posted their messages.
+  for (const auto& kv : by_slot) {
+    const auto& v = kv.second;
+    for (size_t a = 0; a < v.size(); ++a)
+      for (size_t b = 0; b < v.size(); ++b) {
+        if (v[a].order >= v[b].order) continue;
+        const PushCopy &x = v[a].w.op->copy, &y = v[b].w.op->copy;
+        if (x.offset + x.bytes <= y.offset || y.offset + y.bytes <= x.offset) continue;
+        const RvClock& later = st[static_cast<size_t>(v[b].w.writer)].at[v[b].w.index];
+        if (later.strong[static_cast<size_t>(v[a].w.writer)] < static_cast<long>(v[a].w.index) + 1)
+          bad.push_back(strfmt("reuse: slot %d of rank %d: rank %d's copy and rank %d's later one are unordered", kv.first[1],
+                               kv.first[0], v[a].w.writer, v[b].w.writer));
+      }
+  }
+  return bad;
+}
+
+static void expect_no_violations(const std::vector<std::string>& bad, const char* what) {
+  EXPECT(bad.empty());
+  for (size_t i = 0; i < bad.size() && i < 5; ++i) std::fprintf(stderr, "  %s: %s\n", what, bad[i].c_str());
+}
+
+static size_t relayed_copies(const std::vector<RvProgram>& progs) {
+  size_t k = 0;
+  for (size_t w = 0; w < progs.size(); ++w)
+    for (const RvOp& op : progs[w].ops)
+      k += op.kind == RvOp::Copy && op.copy.src != static_cast<int>(w) && op.copy.dst != static_cast<int>(w);
+  return k;
+}
+
+// One recorded session of `n` ranks: the planner in push or relay mode, the
+// caller's body over the recording transport and control plane.
+static std::vector<RvProgram> record_rendezvous(int n, bool relay, int max_signals,
+                                                const std::function<void(Bootstrap&, RendezvousRecorder&)>& body) {
+  std::vector<RvProgram> progs(static_cast<size_t>(n));
+  run_ranks(n, [&](Bootstrap& b, Transport& host) {
+    RendezvousRecorder t(host, relay, max_signals);
+    CollectiveRecorder boot(b, t);
+    body(boot, t);
+    boot.barrier();
+    progs[static_cast<size_t>(b.rank())] = t.prog;
+  });
+  return progs;
+}
+
+static uint64_t record_schedules(Bootstrap& b, Transport& t, int n, size_t bytes) {
+  uint64_t bad = 0;
+  for (Mode m : {Mode::Pair, Mode::Ring, Mode::AllPairs, Mode::Tournament, Mode::Self})
+    for (Direction d : {Direction::Uni, Direction::Bi}) {
+      Schedule s = make_schedule(m, d, n);
+      RunConfig cfg;
+      cfg.bytes = bytes;
+      cfg.iters = 2;
+      cfg.warmup = 1;
+      cfg.verify = true;
+      Buffers bufs(t, cfg.bytes, std::max(1, s.max_recv_slots()));
+      for (auto& ph : run_schedule(t, b, s, cfg, bufs)) bad += ph.total_mismatches;
+    }
+  return bad;
+}
+
+TEST(test_rendezvous_schedules_against_model) {
+  for (int max_signals : {kPushMaxSignals, 2})
+    for (bool relay : {false, true})
+      for (int n : {2, 3, 4, 8}) {
+        std::atomic<uint64_t> mism{0};
+        const auto progs = record_rendezvous(n, relay, max_signals, [&](Bootstrap& b, RendezvousRecorder& t) {
+          mism += record_schedules(b, t, n, 8192);
+        });
+        EXPECT(mism == 0);
+        expect_no_violations(rendezvous_violations(progs), relay ? "relay 8K" : "push 8K");
+        if (!relay) EXPECT(relayed_copies(progs) == 0);
+      }
+}
+
+TEST(test_rendezvous_relayed_stripes_against_model) {
+  // 4 MiB messages: above RouteOptions::min_bytes, so stripes go through ranks
+  // that are neither the sender nor the receiver.
+  for (int max_signals : {kPushMaxSignals, 2})
+    for (int n : {3, 4}) {
+      std::atomic<uint64_t> mism{0};
+      const auto progs = record_rendezvous(n, true, max_signals, [&](Bootstrap& b, RendezvousRecorder& t) {
+        mism += record_schedules(b, t, n, size_t{4} << 20);
+      });
+      EXPECT(mism == 0);
+      EXPECT(relayed_copies(progs) > 0);
+      expect_no_violations(rendezvous_violations(progs), "relay 4M");
+    }
+  // Eight ranks: a tournament round's pairs share the relays (two segments
+  // per link), a single pair has six.
+  for (int max_signals : {kPushMaxSignals, 2}) {
+    std::atomic<uint64_t> mism{0};
+    const auto progs = record_rendezvous(8, true, max_signals, [&](Bootstrap& b, RendezvousRecorder& t) {
+      RunConfig cfg;
+      cfg.bytes = size_t{4} << 20;
+      cfg.iters = 2;
+      cfg.warmup = 1;
+      cfg.verify = true;
+      Schedule s = make_schedule(Mode::Tournament, Direction::Bi, 8);
+      s.phases.resize(2);
+      Buffers bufs(t, cfg.bytes, s.max_recv_slots());
+      for (auto& ph : run_schedule(t, b, s, cfg, bufs)) mism += ph.total_mismatches;
+      Schedule p = make_schedule(Mode::Pair, Direction::Uni, 8);
+      restrict_cells(&p, {{0, 1}, {5, 2}}, true);
+      for (auto& ph : run_schedule(t, b, p, cfg, bufs)) mism += ph.total_mismatches;
+    });
+    EXPECT(mism == 0);
+    EXPECT(relayed_copies(progs) > 0);
+    expect_no_violations(rendezvous_violations(progs), "relay 4M x8");
+  }
+}
+
+// Steps posted back to back: depth 2 over 5 steps of a one-phase schedule
+// reuses every slot (generations 0 1 0 1 0) with no barrier and no host sync
+// in between; the tournament's phases change the flows from step to step.
+static std::vector<RvProgram> record_steps(bool relay, int max_signals, size_t bytes, std::atomic<uint64_t>* mism) {
+  const int n = 4;
+  return record_rendezvous(n, relay, max_signals, [&](Bootstrap& b, RendezvousRecorder& t) {
+    for (int which = 0; which < 2; ++which) {
+      StepOptions so;
+      so.depth = 2;
+      so.batch = which == 1;
+      StepDriver d(t, b, which == 0 ? make_ring_schedule(n, Direction::Bi) : make_tournament_schedule(n, Direction::Bi), bytes,
+                   3, true, 21 + static_cast<uint64_t>(which), so);
+      EXPECT(d.depth() == 2);
+      d.connect();
+      d.poison();
+      d.run_steps(0, 5);
+      d.sync();
+      *mism += d.verify_steps(0, 5).mismatches;
+    }
+  });
+}
+
+TEST(test_rendezvous_step_driver_against_model) {
+  for (int max_signals : {kPushMaxSignals, 2})
+    for (bool relay : {false, true})
+      for (size_t bytes : {size_t{8192}, size_t{2} << 20}) {
+        if (!relay && bytes > 8192) continue;
+        std::atomic<uint64_t> mism{0};
+        const auto progs = record_steps(relay, max_signals, bytes, &mism);
+        EXPECT(mism == 0);
+        EXPECT((relayed_copies(progs) > 0) == (relay && bytes > 8192));
+        expect_no_violations(rendezvous_violations(progs), "steps");
+      }
+}
+
+TEST(test_rendezvous_fuzz_against_model) {
+  // Random groups: self messages, repeated pairs (several messages share one
+  // flag of a group), sizes on both sides of the relay threshold.
+  for (int max_signals : {kPushMaxSignals, 2})
+    for (bool relay : {false, true}) {
+      std::atomic<uint64_t> mism{0};
+      const auto progs = record_rendezvous(4, relay, max_signals, [&](Bootstrap& b, RendezvousRecorder& t) {
+        mism += fuzz_transport(t, b, 40, 0x5EED, size_t{2} << 20);
+      });
+      EXPECT(mism == 0);
+      if (relay) EXPECT(relayed_copies(progs) > 0);
+      expect_no_violations(rendezvous_violations(progs), "fuzz");
+    }
+}
+
+TEST(test_rendezvous_discard_still_runs_the_protocol) {
+  // An injected skip fault moves no payload; every flag is still posted and
+  // waited for, so no peer hangs and the counters stay in step for the
+  // groups that follow.
+  for (bool relay : {false, true}) {
+    const int n = 4;
+    const Phase phase = make_tournament_schedule(n, Direction::Bi).phases[1];
+    const size_t bytes = size_t{2} << 20;
+    auto run = [&](bool discard_only) {
+      return record_rendezvous(n, relay, kPushMaxSignals, [&](Bootstrap& b, RendezvousRecorder& t) {
+        Buffers bufs(t, bytes, phase.max_recv_slots());
+        t.set_discard(true);
+        for (int i = 0; i < 3; ++i) post_phase_iteration(t, phase, bytes, bufs);
+        t.set_discard(false);
+        if (!discard_only)
+          for (int i = 0; i < 2; ++i) post_phase_iteration(t, phase, bytes, bufs);
+        t.sync();
+        b.barrier();
+      });
+    };
+    const auto none = run(true);
+    size_t signals = 0;
+    for (const auto& p : none)
+      for (const RvOp& op : p.ops) signals += op.kind == RvOp::Signal;
+    EXPECT(signals == 2u * 3 * n);  // a pre and a post signal per group and rank
+    expect_no_violations(rendezvous_violations(none), "discard");
+    // Copies again once the fault is lifted, on flags that went on counting.
+    expect_no_violations(rendezvous_violations(run(false)), "discard, then payload");
+  }
+}
+
+// The model has teeth: each of these changes to a recorded set of programs
+// breaks the contract, and the model must say so.
+TEST(test_rendezvous_model_rejects_mutations) {
+  for (bool relay : {false, true}) {
+    std::atomic<uint64_t> mism{0};
+    const auto good = record_steps(relay, kPushMaxSignals, relay ? size_t{2} << 20 : size_t{8192}, &mism);
+    EXPECT(mism == 0 && rendezvous_violations(good).empty());
+    auto has = [](const std::vector<std::string>& bad, const char* what) {
+      for (const auto& s : bad)
+        if (s.rfind(what, 0) == 0) return true;
+      return false;
+    };
+    // The first copy to another rank, in a group that follows another group
+    // to the same receiver, and the signals around it.
+    int w = -1;
+    size_t ci = 0, pre = 0, post = 0;
+    for (int r = 0; r < static_cast<int>(good.size()) && w < 0; ++r) {
+      const auto& ops = good[static_cast<size_t>(r)].ops;
+      for (size_t i = 0; i < ops.size() && w < 0; ++i) {
+        if (ops[i].kind != RvOp::Copy || ops[i].copy.dst == r) continue;
+        const int d = ops[i].copy.dst;
+        long a = -1, z = -1;
+        for (size_t j = 0; j < ops.size(); ++j) {
+          if (ops[j].kind != RvOp::Signal || ops[j].group != ops[i].group) continue;
+          for (const PushFlag& f : ops[j].waits)
+            if (!ops[j].after_copies && f.peer == d && f.kind == kPushReady && f.value >= 2) a = static_cast<long>(j);
+          for (const PushFlag& f : ops[j].posts)
+            if (ops[j].after_copies && f.peer == d && f.kind == kPushDone) z = static_cast<long>(j);
+        }
+        if (a < 0 || z < 0) continue;
+        w = r, ci = i, pre = static_cast<size_t>(a), post = static_cast<size_t>(z);
+      }
+    }
+    EXPECT(w >= 0);
+    if (w < 0) continue;
+    const int d = good[static_cast<size_t>(w)].ops[ci].copy.dst;
+    auto drop = [](std::vector<PushFlag>* v, int peer) {
+      v->erase(std::remove_if(v->begin(), v->end(), [&](const PushFlag& f) { return f.peer == peer; }), v->end());
+    };
+    {  // drop one ready wait
+      auto m = good;
+      drop(&m[static_cast<size_t>(w)].ops[pre].waits, d);
+      EXPECT(has(rendezvous_violations(m), "ready:"));
+    }
+    {  // drop one done wait: the receiver's, for this writer, in the copy's group
+      auto m = good;
+      bool dropped = false;
+      const RvOp& c = good[static_cast<size_t>(w)].ops[ci];
+      long group = -1;
+      for (const RvRecv& rv : good[static_cast<size_t>(d)].recvs)
+        if (rv.src == c.copy.src && rv.slot == c.copy.slot && rv.seq == c.seq) group = rv.group;
+      for (RvOp& op : m[static_cast<size_t>(d)].ops)
+        if (op.kind == RvOp::Signal && op.group == group && op.after_copies) {
+          const size_t before = op.waits.size();
+          drop(&op.waits, w);
+          dropped = dropped || op.waits.size() < before;
+        }
+      EXPECT(dropped);
+      EXPECT(has(rendezvous_violations(m), "done:"));
+    }
+    {  // a wait one lower than it must be: the previous group's ready opens it
+      auto m = good;
+      for (PushFlag& f : m[static_cast<size_t>(w)].ops[pre].waits)
+        if (f.peer == d) --f.value;
+      EXPECT(has(rendezvous_violations(m), "ready:"));
+    }
+    {  // the done post in front of its copy
+      auto m = good;
+      auto& ops = m[static_cast<size_t>(w)].ops;
+      size_t first = ci;
+      while (first > 0 && ops[first - 1].kind == RvOp::Copy) --first;
+      const RvOp moved = ops[post];
+      ops.erase(ops.begin() + static_cast<long>(post));
+      ops.insert(ops.begin() + static_cast<long>(first), moved);
+      EXPECT(has(rendezvous_violations(m), "done:"));
+    }
+    {  // a done piece that does not release first
+      auto m = good;
+      m[static_cast<size_t>(w)].ops[post].release_first = false;
+      EXPECT(has(rendezvous_violations(m), "done:"));
+    }
+  }
+}
+
+// The planner's pieces on their own: one entry per flag with the highest
+// value, at most max_signals posts and waits per piece, every post out before
+// or with the first wait, and a release in front of every done post.
+TEST(test_push_planner_pieces) {
+  std::vector<PushFlag> posts, waits;
+  for (int p = 0; p < 5; ++p) posts.push_back({p, kPushDone, static_cast<unsigned long long>(p + 1)});
+  posts.push_back({1, kPushDone, 9});  // a second message to rank 1: same flag, higher value
+  for (int p = 0; p < 3; ++p) waits.push_back({p, kPushDone, 4});
+  const auto one = PushPlanner::pieces(posts, waits, kPushMaxSignals, true);
+  EXPECT(one.size() == 1 && one[0].posts.size() == 5 && one[0].waits.size() == 3 && one[0].release_first);
+  EXPECT(one[0].posts[1].peer == 1 && one[0].posts[1].value == 9);
+  const auto cut = PushPlanner::pieces(posts, waits, 2, true);
+  EXPECT(cut.size() == 4);  // posts 2 + 2 + 1, waits 0 + 0 + 2 + 1
+  bool waited = false;
+  for (const auto& piece : cut) {
+    EXPECT(piece.posts.size() <= 2 && piece.waits.size() <= 2);
+    EXPECT(piece.posts.empty() || piece.release_first);  // the overflow pieces carry done posts too
+    waited = waited || !piece.waits.empty();
+    if (waited && &piece != &cut[2]) EXPECT(piece.posts.empty());
+  }
+  EXPECT(cut.back().release_first);
+  for (const auto& piece : PushPlanner::pieces(posts, waits, 2, false)) EXPECT(!piece.release_first);
+  EXPECT(PushPlanner::pieces({}, {}, 2, true).empty());
+}
+
 
 int main(int argc, char** argv) {
   const char* only = argc > 1 ? argv[1] : nullptr;
