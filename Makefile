@@ -26,7 +26,7 @@ HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
 CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load) kernels.o diagnose_hip.o pingpong.o load_hip.o)
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o diagnose_hip.o pingpong.o load_hip.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in

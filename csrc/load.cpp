@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "hip_check.hpp"
+#include "hip_stream.hpp"
 #include "kernels.hpp"
 
 namespace p2p {
@@ -239,25 +240,10 @@ class HipBackgroundLoad final : public BackgroundLoad {
     return time_train(n) / static_cast<double>(n);
   }
 
-  // The transports' bounded wait (sync()): a poll, an abort request or the
-  // timeout ends it with an error.
+  // The transports' bounded wait (hip_stream.hpp): a stream error, an abort
+  // request or the timeout cancels the train and ends it with an error.
   void drain() { drain(stream_); }
-  void drain(hipStream_t st) {
-    const double t0 = now_seconds();
-    for (long it = 0;; ++it) {
-      const hipError_t e = hipStreamQuery(st);
-      if (e == hipSuccess) return;
-      if (e != hipErrorNotReady) P2P_FATAL(strfmt("load stream error: %s", hipGetErrorString(e)));
-      if ((it & 255) == 0) {
-        const double now = now_seconds();
-        if (abort_requested() || now - t0 > timeout_) {
-          if (cancel_) __atomic_store_n(cancel_, 1u, __ATOMIC_RELEASE);
-          P2P_FATAL(strfmt("background load did not finish within %.0f s", timeout_));
-        }
-        if (now - t0 > 20e-3) std::this_thread::sleep_for(std::chrono::microseconds(20));
-      }
-    }
-  }
+  void drain(hipStream_t st) { wait_stream(st, timeout_, -1, wait_policy_); }
   bool drain_quietly() {
     if (!stream_) return true;
     const double deadline = now_seconds() + std::min(timeout_, 10.0);
@@ -272,6 +258,9 @@ class HipBackgroundLoad final : public BackgroundLoad {
   bool mfma_;
   int wgs_;
   double timeout_;
+  const WaitPolicy wait_policy_{"background load", "", "load stream", /*answers_abort=*/false, nullptr, [this] {
+                                  if (cancel_) __atomic_store_n(cancel_, 1u, __ATOMIC_RELEASE);
+                                }};
   hipStream_t beside_;  // the stream the transfers run on (null: any stream will do)
   hipStream_t stream_ = nullptr;
   unsigned char* words_ = nullptr;  // pinned: cancel at +0, done at +64

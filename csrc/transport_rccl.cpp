@@ -62,14 +62,11 @@
 
 #include "bootstrap.hpp"
 #include "common.hpp"
-#include "device_checks.hpp"
 #include "hip_check.hpp"
-#include "kernels.hpp"
-#include "load.hpp"
+#include "hip_stream.hpp"
 #include "provenance.hpp"
 #include "rccl_log.hpp"
 #include "report.hpp"
-#include "stream_gate.hpp"
 #include "topology.hpp"
 #include "transport.hpp"
 #include "units.hpp"
@@ -77,24 +74,27 @@
 namespace p2p {
 namespace {
 
-class RcclTransport final : public Transport {
+class RcclTransport final : public GpuTransport {
  public:
   RcclTransport(Bootstrap& boot, const TransportOptions& opt)
-      : rank_(boot.rank()), n_(boot.size()), timeout_(opt.timeout_s),
-        checks_(static_cast<dev::VerifyImpl>(opt.verify_impl)) {
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0)
-      P2P_FATAL(strfmt("rank %d: no HIP device visible (%s)", rank_, e == hipSuccess ? "0 devices" : hipGetErrorString(e)));
-    device_ = opt.device >= 0 ? opt.device : 0;
-    // The reference never checks this and lets cudaSetDevice fail.
-    if (device_ >= ndev)
-      P2P_FATAL(strfmt("rank %d wants GPU %d but only %d are visible: more ranks per host than GPUs", rank_, device_, ndev));
+      : GpuTransport(boot, opt, /*keep_graphs=*/true,  // see the destructor
+                     "rank %d: no HIP device visible (%s)",
+                     // The reference never checks this and lets cudaSetDevice fail.
+                     "rank %d wants GPU %d but only %d are visible: more ranks per host than GPUs") {
     int ncomms = opt.rccl_comms;
     if (const char* kc = std::getenv("P2P_RCCL_COMMS")) ncomms = std::atoi(kc);
     P2P_CHECK(ncomms >= 1 && ncomms <= kMaxComms, strfmt("rccl communicators per rank: 1..%d", kMaxComms));
     P2P_CHECK(ncomms == 1 || !opt.two_streams, "--two-streams (the reference layout) uses one communicator");
-    HIPCHECK(hipSetDevice(device_));
+    wait_policy_.tail = " (peer hung or dead?); aborting";
+    wait_policy_.poll_error = [this] {
+      const std::string err = async_error();
+      return err.empty() ? err : "RCCL asynchronous error while waiting: " + err;
+    };
+    // Before any failure the communicators are aborted: RCCL's kernels poll
+    // the abort flag and exit, so the streams (and any hardware queue they
+    // share with another session's streams) drain instead of staying stuck
+    // behind a transfer that will never complete.
+    wait_policy_.before_failure = [this] { abort_all(); };
     open_streams(opt, ncomms);
     stale_.assign(static_cast<size_t>(ncomms), true);
     pending_.assign(static_cast<size_t>(ncomms), false);
@@ -118,12 +118,7 @@ class RcclTransport final : public Transport {
     // Graphs that captured RCCL work hold references to the communicator's
     // persistent resources: release them before the communicator, or
     // ncclCommDestroy waits for them forever.
-    for (auto ex : execs_)
-      if (ex) (void)hipGraphExecDestroy(ex);
-    for (auto g : graphs_)
-      if (g) (void)hipGraphDestroy(g);
-    execs_.clear();
-    graphs_.clear();
+    destroy_graphs();
     // An aborted communicator took its registrations with it.
     for (auto& r : reg_sets_)
       for (auto& ch : r.handles)
@@ -141,7 +136,6 @@ class RcclTransport final : public Transport {
         ncclCommDestroy(c);
         c = nullptr;
       }
-    for (auto ev : events_) (void)hipEventDestroy(ev);
     for (auto& v : side_ev_)
       for (auto ev : v)
         if (ev) (void)hipEventDestroy(ev);
@@ -152,14 +146,10 @@ class RcclTransport final : public Transport {
     if (join_) (void)hipEventDestroy(join_);
     for (auto cs : cstreams_)
       if (cs != stream_) (void)hipStreamDestroy(cs);
-    if (stream_) (void)hipStreamDestroy(stream_);
+    destroy_stream_objects();
   }
 
   std::string name() const override { return "rccl"; }
-  int rank() const override { return rank_; }
-  int nranks() const override { return n_; }
-  std::string device_desc() const override { return desc_; }
-  std::string device_key() const override { return gpu_memory_key(device_); }
 
   bool mem_info(size_t* free_b, size_t* total_b) override { return hipMemGetInfo(free_b, total_b) == hipSuccess; }
   void* alloc(size_t bytes) override {
@@ -212,31 +202,6 @@ class RcclTransport final : public Transport {
   }
   // Not aborted (abort_all clears the communicator's slot).
   bool live(ncclComm_t c) const { return c && std::find(comms_.begin(), comms_.end(), c) != comms_.end(); }
-  void fill(void* p, size_t bytes, uint64_t seed) override {
-    buffer_work();
-    dev::launch_fill(p, bytes, seed, stream_);
-  }
-  void zero(void* p, size_t bytes) override {
-    buffer_work();
-    HIPCHECK(hipMemsetAsync(p, 0, bytes, stream_));
-  }
-
-  // The checks run on the buffer stream behind the bounded, abort-aware
-  // sync() (device_checks.hpp).
-  VerifyResult verify(const void* p, size_t bytes, uint64_t seed) override {
-    buffer_work();
-    return checks_.verify(p, bytes, seed, stream_, [this] { sync(); });
-  }
-  std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs) override {
-    if (jobs.empty()) return {};
-    buffer_work();
-    return checks_.verify_many(jobs, stream_, [this] { sync(); });
-  }
-  std::vector<DiagExtent> diagnose(const void* p, size_t bytes, uint64_t seed,
-                                   const std::vector<DiagCandidate>& candidates) override {
-    buffer_work();
-    return checks_.diagnose(p, bytes, seed, candidates, stream_, [this] { sync(); });
-  }
 
   void group_begin() override {
     check_live("group_begin");
@@ -323,17 +288,14 @@ class RcclTransport final : public Transport {
   // work up to a and all work up to b, so back-to-back intervals add up to
   // the whole run even when side streams finish a step after the main one.
   int mark() override {
-    const size_t m = static_cast<size_t>(next_event_);
-    if (m == events_.size()) {
-      hipEvent_t ev;
-      HIPCHECK(hipEventCreateWithFlags(&ev, timing_event_flags()));
-      events_.push_back(ev);
+    const int id = GpuTransport::mark();  // the main stream's event
+    const size_t m = static_cast<size_t>(id);
+    if (m == side_ev_.size()) {
       side_ev_.emplace_back(cstreams_.size(), nullptr);
       side_rec_.emplace_back(cstreams_.size(), 0);
       side_ref_.emplace_back(cstreams_.size(), -1);
     }
     last_side_.resize(cstreams_.size(), -1);
-    HIPCHECK(hipEventRecord(events_[m], stream_));
     for (size_t j = 0; j < cstreams_.size(); ++j) {
       side_rec_[m][j] = 0;
       if (j < pending_.size() && pending_[j]) {
@@ -345,17 +307,17 @@ class RcclTransport final : public Transport {
       }
       side_ref_[m][j] = last_side_[j];
     }
-    return next_event_++;
+    return id;
   }
   double elapsed_ms(int a, int b) override {
     const size_t ia = static_cast<size_t>(a), ib = static_cast<size_t>(b);
-    hipEvent_t ref = events_.at(ia);
+    hipEvent_t ref = mark_event(a);
     auto since_ref = [&](hipEvent_t e) {
       float ms = 0;
       HIPCHECK(hipEventElapsedTime(&ms, ref, e));
       return static_cast<double>(ms);
     };
-    double start = 0, end = since_ref(events_.at(ib));
+    double start = 0, end = since_ref(mark_event(b));
     for (size_t j = 0; j < cstreams_.size(); ++j) {
       const int ra = side_ref_[ia][j], rb = side_ref_[ib][j];
       if (ra >= 0) start = std::max(start, since_ref(side_ev_[static_cast<size_t>(ra)][j]));
@@ -368,7 +330,7 @@ class RcclTransport final : public Transport {
   // stream and the side streams that ran since their last mark (callers
   // clear between runs, with the streams drained or about to be).
   void clear_marks() override {
-    next_event_ = 0;
+    GpuTransport::clear_marks();
     std::fill(last_side_.begin(), last_side_.end(), -1);
   }
 
@@ -379,67 +341,13 @@ class RcclTransport final : public Transport {
   // streams crashed inside RCCL 2.26 on MI355X (scripts/comms_probe.py
   // --graph 1, profiles/r1_comms/).
   bool supports_graphs() const override { return comms_.size() == 1; }
-  void capture_begin() override { HIPCHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal)); }
-  int capture_end() override {
-    hipGraph_t g = nullptr;
-    HIPCHECK(hipStreamEndCapture(stream_, &g));
-    hipGraphExec_t ex = nullptr;
-    HIPCHECK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
-    graphs_.push_back(g);
-    execs_.push_back(ex);
-    return static_cast<int>(execs_.size()) - 1;
-  }
-  void graph_launch(int h) override {
-    hipGraphExec_t ex = execs_.at(static_cast<size_t>(h));
-    P2P_CHECK(ex != nullptr, "graph_launch: the graph was released");
-    HIPCHECK(hipGraphLaunch(ex, stream_));
-  }
-  // The executable graph and the graph that captured RCCL work (both hold
-  // references to the communicator's resources, see the destructor).
-  void graph_release(int h) override {
-    hipGraphExec_t& ex = execs_.at(static_cast<size_t>(h));
-    hipGraph_t& g = graphs_.at(static_cast<size_t>(h));
-    if (ex) HIPCHECK(hipGraphExecDestroy(ex));
-    if (g) HIPCHECK(hipGraphDestroy(g));
-    ex = nullptr;
-    g = nullptr;
-  }
 
   void sync() override {
-    // Bounded poll instead of hipStreamSynchronize: spins for the first 20 ms
-    // (so per-message syncs in wallclock mode are not inflated by sleeps),
-    // then backs off; checks RCCL's async error so a failed peer aborts.
+    // The bounded poll (hip_stream.hpp), which also checks RCCL's async error
+    // so that a failed peer aborts.
     check_live("sync");
     join_all();
-    double t0 = now_seconds();
-    double deadline = t0 + timeout_;
-    for (long it = 0;; ++it) {
-      hipError_t e = hipStreamQuery(stream_);
-      if (e == hipSuccess) return;
-      if (e != hipErrorNotReady) P2P_FATAL(strfmt("stream error: %s", hipGetErrorString(e)));
-      if ((it & 255) == 0) {
-        if (abort_requested()) {
-          abort_all();
-          note_abort_done();
-          P2P_FATAL(strfmt("rank %d: aborted while waiting (the run's deadline passed)", rank_));
-        }
-        // Either way the communicators are aborted first: RCCL's kernels poll
-        // the abort flag and exit, so the streams (and any hardware queue they
-        // share with another session's streams) drain instead of staying
-        // stuck behind a transfer that will never complete.
-        std::string err = async_error();
-        if (!err.empty()) {
-          abort_all();
-          P2P_FATAL("RCCL asynchronous error while waiting: " + err);
-        }
-        double now = now_seconds();
-        if (now > deadline) {
-          abort_all();
-          P2P_FATAL(strfmt("rank %d: stream did not finish within %.0f s (peer hung or dead?); aborting", rank_, timeout_));
-        }
-        if (now - t0 > 20e-3) std::this_thread::sleep_for(std::chrono::microseconds(20));
-      }
-    }
+    wait_stream(stream_, timeout_, rank_, wait_policy_);
   }
 
   // Every stream idle, bounded like sync() but without throwing: past the
@@ -489,23 +397,6 @@ class RcclTransport final : public Transport {
   }
   size_t max_chunk(int peer) const override { return chunk_for(peer); }
 
-  bool gate_arm(double timeout_s) override {
-    gate_.arm(stream_, timeout_s);
-    return true;
-  }
-  void gate_release() override { gate_.release(); }
-  bool gate_timed_out() override { return gate_.timed_out(); }
-  bool stream_idle() override {
-    const hipError_t e = hipStreamQuery(stream_);
-    if (e != hipSuccess && e != hipErrorNotReady) P2P_FATAL(strfmt("stream error: %s", hipGetErrorString(e)));
-    return e == hipSuccess;
-  }
-  std::unique_ptr<BackgroundLoad> make_load(const std::string& kind, int wgs) override {
-    HIPCHECK(hipSetDevice(device_));
-    return make_background_load(kind, wgs, timeout_, stream_);
-  }
-  void set_timeout(double seconds) override { timeout_ = seconds; }
-
   std::string async_error() override {
     for (auto c : comms_) {
       if (!c) return "communicator aborted";
@@ -524,7 +415,6 @@ class RcclTransport final : public Transport {
   // a stream of its own or each communicator a CU mask, P2P_RCCL_MAIN_IDLE /
   // P2P_RCCL_CU_MASK: neutral or slower, profiles/r2_cu_mask/.)
   void open_streams(const TransportOptions& opt, int ncomms) {
-    HIPCHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     if (opt.two_streams) {
       HIPCHECK(hipStreamCreateWithFlags(&recv_stream_, hipStreamNonBlocking));
       HIPCHECK(hipEventCreateWithFlags(&join_, hipEventDisableTiming));
@@ -728,8 +618,6 @@ class RcclTransport final : public Transport {
                  rank_, peers.c_str());
   }
 
- public:
-
  private:
   // link_report(): the communicators' channel counts, and per peer the
   // transport and channels RCCL's connection lines show, next to the op
@@ -784,7 +672,7 @@ class RcclTransport final : public Transport {
 
   // The main stream is about to touch payload buffers: side streams must wait
   // for it before their next transfer.
-  void buffer_work() {
+  void before_buffer_work() override {
     join_all();
     forked_ = false;
     std::fill(stale_.begin(), stale_.end(), true);
@@ -928,11 +816,8 @@ class RcclTransport final : public Transport {
     }
   }
 
-  int rank_, n_;
-  double timeout_;
-  int device_ = 0;
+  WaitPolicy wait_policy_;  // sync(): RCCL's async error on a poll, abort_all() before any failure
   bool nonblocking_ = true;
-  hipStream_t stream_ = nullptr;
   hipStream_t recv_stream_ = nullptr;  // two-stream (reference) layout only
   hipEvent_t join_ = nullptr;
   bool recv_on_side_ = false;
@@ -988,21 +873,14 @@ class RcclTransport final : public Transport {
   int register_ = 0;                 // P2P_RCCL_REGISTER: 0 off, 1 ncclCommRegister, 2 + ncclMemAlloc
   std::vector<RegSet> reg_sets_;
   std::vector<void*> nccl_alloc_;    // buffers from ncclMemAlloc
-  std::vector<hipEvent_t> events_;                 // per mark: on the main stream
   std::vector<std::vector<hipEvent_t>> side_ev_;   // per mark: on each side stream (lazily created)
   std::vector<std::vector<char>> side_rec_;        // per mark: side event j recorded by that mark
   std::vector<std::vector<int>> side_ref_;         // per mark: the mark whose side event j stands for stream j (-1 none)
   std::vector<int> last_side_;                     // latest mark that recorded on side stream j
   std::vector<bool> pending_;                      // side stream ran work since the last mark
   std::vector<bool> unjoined_;                     // side stream ran work since the last join
-  std::vector<hipGraph_t> graphs_;
-  std::vector<hipGraphExec_t> execs_;
-  int next_event_ = 0;
-  DeviceChecks checks_;
-  std::string desc_;
   int hook_ = 0;
   std::atomic<bool> aborted_{false};  // abort_all ran: check_live refuses new work
-  StreamGate gate_;
 };
 
 }  // namespace

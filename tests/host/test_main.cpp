@@ -22,6 +22,7 @@
 #include "block_split.hpp"
 #include "bootstrap.hpp"
 #include "common.hpp"
+#include "ipc_blocks.hpp"
 #include "prng.hpp"
 #include "push_plan.hpp"
 #include "rccl_log.hpp"
@@ -2607,6 +2608,248 @@ TEST(test_push_planner_pieces) {
   EXPECT(cut.back().release_first);
   for (const auto& piece : PushPlanner::pieces(posts, waits, 2, false)) EXPECT(!piece.release_first);
   EXPECT(PushPlanner::pieces({}, {}, 2, true).empty());
+}
+
+// ------------------------- IpcBlocks: the exporting allocator and its pool ----
+//
+// The IPC transport's block policy (ipc_blocks.hpp) over counting fakes: the
+// fake allocator hands out 1, 2, 3, ... as pointers and keeps the live set,
+// the fake export writes the pointer into the handle.
+namespace {
+struct FakeIpcMemory {
+  int allocs = 0, frees = 0, exports = 0;
+  int fail_allocs = 0;     // the next so many allocations fail
+  int refuse_exports = 0;  // the next so many exports are refused
+  std::set<void*> live;
+  std::vector<std::string> log;            // "alloc <n>", "free <n>", in order
+  std::vector<std::pair<size_t, size_t>> refusals;  // what the callback reported
+  std::vector<size_t> sizes;               // of every allocation that succeeded
+
+  static void* ptr(int k) { return reinterpret_cast<void*>(static_cast<uintptr_t>(k)); }
+  static int num(void* p) { return static_cast<int>(reinterpret_cast<uintptr_t>(p)); }
+  static uintptr_t handle_value(const IpcHandle& h) {
+    uintptr_t v = 0;
+    std::memcpy(&v, h.bytes, sizeof(v));
+    return v;
+  }
+
+  IpcBlocks blocks(size_t cap, bool size_fix = true) {
+    return IpcBlocks(
+        cap, size_fix,
+        [this](void** p, size_t size) -> const char* {
+          if (fail_allocs > 0) {
+            --fail_allocs;
+            log.push_back("alloc failed");
+            return "out of memory";
+          }
+          *p = ptr(++allocs);
+          live.insert(*p);
+          sizes.push_back(size);
+          log.push_back("alloc " + std::to_string(allocs));
+          return nullptr;
+        },
+        [this](void* p) {
+          ++frees;
+          EXPECT(live.erase(p) == 1);  // freed once, and only what was allocated
+          log.push_back("free " + std::to_string(num(p)));
+        },
+        [this](void* p, IpcHandle* h) -> const char* {
+          ++exports;
+          if (refuse_exports > 0) {
+            --refuse_exports;
+            return "invalid argument";
+          }
+          const uintptr_t v = reinterpret_cast<uintptr_t>(p);
+          std::memset(h->bytes, 0, sizeof(h->bytes));
+          std::memcpy(h->bytes, &v, sizeof(v));
+          return nullptr;
+        },
+        [this](size_t blocks, size_t size) { refusals.emplace_back(blocks, size); });
+  }
+};
+
+template <class F>
+std::string fatal_text(F&& f) {
+  set_throw_on_fatal(true);
+  std::string what;
+  try {
+    f();
+  } catch (const Error& e) {
+    what = e.what();
+    if (what.empty()) what = "?";
+  }
+  set_throw_on_fatal(false);
+  return what;
+}
+bool has_text(const std::string& s, const char* part) { return s.find(part) != std::string::npos; }
+}  // namespace
+
+TEST(test_ipc_blocks_size_rule) {
+  constexpr size_t M = size_t{1} << 20, G = size_t{1} << 30;
+  const std::vector<std::array<size_t, 3>> cases = {
+      // request, with the fix, without it
+      {1, 2 * M, 2 * M},
+      {2 * M + 1, 4 * M, 4 * M},
+      {2 * G, 4 * G, 2 * G},
+      {2 * G - 2 * M, 2 * G - 2 * M, 2 * G - 2 * M},
+      {3 * G + 768 * M, 4 * G, 3 * G + 768 * M},
+      {4 * G, 4 * G, 4 * G},
+      {4 * G + 2 * M, 4 * G + 2 * M, 4 * G + 2 * M},
+      {5 * G, 5 * G, 5 * G},
+      {7 * G, 8 * G, 7 * G},
+  };
+  for (const auto& c : cases) {
+    EXPECT(IpcBlocks::size_for(c[0], true) == c[1]);
+    EXPECT(IpcBlocks::size_for(c[0], false) == c[2]);
+  }
+  // alloc() asks the allocator for exactly that size, fix on and off.
+  FakeIpcMemory on, off;
+  IpcBlocks a = on.blocks(0, true), b = off.blocks(0, false);
+  a.release(a.alloc(2 * G));
+  b.release(b.alloc(2 * G));
+  EXPECT(on.sizes == std::vector<size_t>{4 * G} && off.sizes == std::vector<size_t>{2 * G});
+  EXPECT(on.live.empty() && off.live.empty());
+}
+
+TEST(test_ipc_blocks_pool_reuse_and_cap) {
+  constexpr size_t M = size_t{1} << 20;
+  {
+    FakeIpcMemory mem;
+    IpcBlocks blocks = mem.blocks(size_t{64} * M);
+    void* p = blocks.alloc(3 * M);  // rounds to 4 MiB
+    const uintptr_t h = FakeIpcMemory::handle_value(blocks.handle_of(p));
+    EXPECT(h == reinterpret_cast<uintptr_t>(p) && mem.allocs == 1 && mem.exports == 1);
+    blocks.release(p);
+    EXPECT(mem.frees == 0 && blocks.pooled_bytes() == 4 * M);
+    void* q = blocks.alloc(4 * M);  // the same rounded size: the pooled block, no allocate call
+    EXPECT(q == p && FakeIpcMemory::handle_value(blocks.handle_of(q)) == h);
+    EXPECT(mem.allocs == 1 && mem.exports == 1 && blocks.pooled_bytes() == 0);
+    blocks.release(q);
+    void* r = blocks.alloc(5 * M);  // another size allocates; the pool keeps its block
+    EXPECT(r != p && mem.allocs == 2 && mem.sizes.back() == 6 * M && blocks.pooled_bytes() == 4 * M);
+    blocks.release(nullptr);  // a no-op
+    blocks.release(r);
+    EXPECT(blocks.pooled_bytes() == 10 * M && mem.frees == 0);
+    blocks.drain();  // exactly the pooled blocks
+    EXPECT(mem.frees == 2 && mem.live.empty() && blocks.pooled_bytes() == 0);
+  }
+  {
+    FakeIpcMemory mem;  // cap 0 keeps nothing
+    IpcBlocks blocks = mem.blocks(0);
+    void* p = blocks.alloc(1);
+    blocks.release(p);
+    EXPECT(mem.frees == 1 && mem.live.empty() && blocks.pooled_bytes() == 0);
+  }
+  {
+    FakeIpcMemory mem;  // a release that would pass the cap frees that block
+    IpcBlocks blocks = mem.blocks(5 * M);
+    void* a = blocks.alloc(2 * M);
+    void* b = blocks.alloc(2 * M);
+    void* c = blocks.alloc(2 * M);
+    blocks.release(a);
+    blocks.release(b);
+    EXPECT(blocks.pooled_bytes() == 4 * M && mem.frees == 0);
+    blocks.release(c);
+    EXPECT(blocks.pooled_bytes() == 4 * M && mem.frees == 1 && mem.live.count(c) == 0);
+    void* live = blocks.alloc(2 * M);  // from the pool; stays live across the drain
+    blocks.drain();
+    EXPECT(mem.frees == 2 && mem.live == std::set<void*>{live});
+    EXPECT(FakeIpcMemory::handle_value(blocks.handle_of(live)) == reinterpret_cast<uintptr_t>(live));
+    blocks.release(live);
+    blocks.drain();
+    EXPECT(mem.live.empty());
+  }
+}
+
+TEST(test_ipc_blocks_allocation_failure) {
+  constexpr size_t M = size_t{1} << 20;
+  {
+    FakeIpcMemory mem;  // a pool to give back: drained, then one retry
+    IpcBlocks blocks = mem.blocks(size_t{64} * M);
+    blocks.release(blocks.alloc(2 * M));
+    mem.log.clear();
+    mem.fail_allocs = 1;
+    void* p = blocks.alloc(4 * M);
+    EXPECT((mem.log == std::vector<std::string>{"alloc failed", "free 1", "alloc 2"}));
+    EXPECT(p == FakeIpcMemory::ptr(2) && blocks.pooled_bytes() == 0 && mem.live == std::set<void*>{p});
+    blocks.release(p);
+    mem.log.clear();
+    mem.fail_allocs = 2;  // the retry fails too: fatal, and no third attempt
+    const std::string what = fatal_text([&] { blocks.alloc(8 * M); });
+    EXPECT(has_text(what, "device allocation of 8388608 bytes failed: out of memory"));
+    EXPECT((mem.log == std::vector<std::string>{"alloc failed", "free 2", "alloc failed"}));
+    EXPECT(mem.live.empty() && mem.fail_allocs == 0);
+  }
+  {
+    FakeIpcMemory mem;  // an empty pool: fatal at once
+    IpcBlocks blocks = mem.blocks(size_t{64} * M);
+    mem.fail_allocs = 1;
+    const std::string what = fatal_text([&] { blocks.alloc(1); });
+    EXPECT(has_text(what, "device allocation of 2097152 bytes failed"));
+    EXPECT((mem.log == std::vector<std::string>{"alloc failed"}) && mem.live.empty());
+  }
+}
+
+TEST(test_ipc_blocks_export_refusals) {
+  constexpr size_t M = size_t{1} << 20;
+  for (int k : {1, 2, 7}) {
+    FakeIpcMemory mem;
+    IpcBlocks blocks = mem.blocks(0);
+    mem.refuse_exports = k;
+    void* p = blocks.alloc(2 * M);
+    // The (k+1)th block; the k refused ones are held until it exists.
+    EXPECT(p == FakeIpcMemory::ptr(k + 1) && mem.allocs == k + 1 && mem.exports == k + 1);
+    std::vector<std::string> want;
+    for (int i = 1; i <= k + 1; ++i) want.push_back("alloc " + std::to_string(i));
+    for (int i = 1; i <= k; ++i) want.push_back("free " + std::to_string(i));
+    EXPECT(mem.log == want);
+    EXPECT((mem.refusals == std::vector<std::pair<size_t, size_t>>{{static_cast<size_t>(k), 2 * M}}));
+    EXPECT(mem.live == std::set<void*>{p});
+    EXPECT(FakeIpcMemory::handle_value(blocks.handle_of(p)) == reinterpret_cast<uintptr_t>(p));
+    blocks.release(p);
+    EXPECT(mem.live.empty());
+  }
+  {
+    FakeIpcMemory mem;  // the eighth refusal in a row is fatal; everything held is freed
+    IpcBlocks blocks = mem.blocks(0);
+    mem.refuse_exports = 8;
+    const std::string what = fatal_text([&] { blocks.alloc(2 * M); });
+    EXPECT(has_text(what, "hipIpcGetMemHandle refused 8 fresh 2097152-byte blocks: invalid argument"));
+    EXPECT(mem.allocs == 8 && mem.frees == 8 && mem.live.empty() && mem.refusals.empty());
+  }
+  {
+    FakeIpcMemory mem;  // the signal pages' path: another allocator, the same retry, no live-map entry
+    IpcBlocks blocks = mem.blocks(0);
+    mem.refuse_exports = 2;
+    int page_allocs = 0;
+    IpcHandle h{};
+    void* p = blocks.exportable(4096, &h, [&](void** q, size_t size) -> const char* {
+      EXPECT(size == 4096);
+      *q = FakeIpcMemory::ptr(100 + ++page_allocs);
+      mem.live.insert(*q);
+      return nullptr;
+    });
+    EXPECT(p == FakeIpcMemory::ptr(103) && page_allocs == 3 && mem.frees == 2 && mem.allocs == 0);
+    EXPECT((mem.refusals == std::vector<std::pair<size_t, size_t>>{{2, 4096}}) && mem.live == std::set<void*>{p});
+    EXPECT(FakeIpcMemory::handle_value(h) == 103);
+    EXPECT(has_text(fatal_text([&] { blocks.handle_of(p); }), "exports only buffers it allocated"));
+  }
+}
+
+TEST(test_ipc_blocks_unknown_pointers) {
+  FakeIpcMemory mem;
+  IpcBlocks blocks = mem.blocks(size_t{1} << 30);
+  void* p = blocks.alloc(1);
+  void* stranger = FakeIpcMemory::ptr(999);
+  EXPECT(has_text(fatal_text([&] { blocks.release(stranger); }), "release of a buffer this transport did not allocate"));
+  EXPECT(has_text(fatal_text([&] { blocks.handle_of(stranger); }), "ipc transport exports only buffers it allocated"));
+  blocks.release(p);
+  // A pooled block is not a live one: no handle, no second release.
+  EXPECT(has_text(fatal_text([&] { blocks.handle_of(p); }), "exports only buffers it allocated"));
+  EXPECT(has_text(fatal_text([&] { blocks.release(p); }), "did not allocate"));
+  EXPECT(mem.frees == 0 && blocks.pooled_bytes() == (size_t{2} << 20));
+  blocks.drain();
+  EXPECT(mem.frees == 1 && mem.live.empty());
 }
 
 
