@@ -26,7 +26,7 @@ HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
 CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o diagnose_hip.o pingpong.o load_hip.o)
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o diagnose_hip.o pingpong.o stream.o load_hip.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in
@@ -108,6 +108,9 @@ $(BUILD)/gpu/load_hip.o: csrc/load.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/gpu/pingpong.o: csrc/pingpong.hip $(HEADERS) | $(BUILD)/gpu
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/gpu/stream.o: csrc/stream.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/gpu/bootstrap_mpi.o: csrc/bootstrap_mpi.cpp $(HEADERS) | $(BUILD)/gpu

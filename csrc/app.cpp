@@ -13,6 +13,7 @@
 #include "provenance.hpp"
 #include "rccl_log.hpp"
 #include "report.hpp"
+#include "stream_layout.hpp"
 #include "topology.hpp"
 #include "transport.hpp"
 #include "units.hpp"
@@ -93,6 +94,17 @@ timing
       --device-latency   add a device-initiated ping-pong matrix (--transport ipc:
                          one wave per GPU writes into the peer's memory, no host
                          or runtime in the loop)
+      --device-stream    add a device-initiated stream table (--transport ipc): per flow
+                         --stream-channels credit-flow rings of --stream-depth slots in the
+                         receiver's memory, one sender and one receiver wave each, no host in
+                         the loop: GB/s, Mmsg/s, per-message gap and the receiver's own rate
+                         per size; -d uni measures a pair's directions one at a time, bi both
+                         at once.  Every cell is verified first (every 16 B vector of up to
+                         256 messages).  Not with --reference
+      --stream-sizes LIST  like --sizes; each rounded up to 16, at most 1M    [16:64K]
+      --stream-depth D   messages in flight per channel, 1..64, D x size <= 4M [8]
+      --stream-channels W  channels per flow, 1..8                            [1]
+      --stream-iters N   messages per channel, 1..100000                      [2000]
       --latency-preposted B  also the ping-pong posted B exchanges at a time behind a
                          stream gate (GPU transports), released together: the
                          operation's GPU-timeline latency without the host's posting
@@ -200,6 +212,7 @@ std::vector<Mode> parse_modes(const std::string& s) {
 bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out) {
   *exit_code = 0;
   bool size_given = false;
+  bool stream_opts = false;  // a --stream-* option was given
   // P2P_DEVICE: the default of --device (a multi-GPU rehearsal on one GPU
   // puts every rank on device 0 without editing the command lines).
   if (const char* d = std::getenv("P2P_DEVICE"); d && *d) cfg->device = std::atoi(d);
@@ -262,7 +275,8 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     static const char* kValued[] = {"-m", "--mode", "-d", "--dir", "-b", "--size", "--sizes", "-n", "--iters", "-w",
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
-                                    "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load"};
+                                    "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load", "--stream-sizes",
+                                    "--stream-depth", "--stream-channels", "--stream-iters"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -324,6 +338,20 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       cfg->latency = true;
     } else if (a == "--device-latency") {
       cfg->device_latency = true;
+    } else if (a == "--device-stream") {
+      cfg->device_stream = true;
+    } else if (a == "--stream-sizes") {
+      cfg->stream_sizes = parse_size_list(next());
+      stream_opts = true;
+    } else if (a == "--stream-depth") {
+      cfg->stream_depth = int_arg(INT_MIN);
+      stream_opts = true;
+    } else if (a == "--stream-channels") {
+      cfg->stream_channels = int_arg(INT_MIN);
+      stream_opts = true;
+    } else if (a == "--stream-iters") {
+      cfg->stream_iters = int_arg(INT_MIN);
+      stream_opts = true;
     } else if (a == "--latency-preposted") {
       cfg->latency_preposted = int_arg(0);
       cfg->latency = true;
@@ -439,6 +467,32 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                  cfg->transport.c_str());
     *exit_code = 1;
     return false;
+  }
+  // The stream options mean nothing without --device-stream, and their limits
+  // are the kernel's (stream_layout.hpp): named here, before any rank starts.
+  if (stream_opts && !cfg->device_stream) {
+    std::fprintf(stderr, "p2p_matrix: --stream-sizes, --stream-depth, --stream-channels and --stream-iters need --device-stream\n");
+    *exit_code = 1;
+    return false;
+  }
+  if (cfg->device_stream) {
+    std::string why;
+    if (cfg->transport != "ipc")
+      why = strfmt("--device-stream needs a one-sided transport (--transport ipc); %s has none", cfg->transport.c_str());
+    else if (cfg->reference_buffers)  // set by --reference alone
+      why = "--device-stream cannot be combined with --reference: that is the reference's run, which has no such table";
+    else if (cfg->stream_iters < 1 || cfg->stream_iters > StreamLayout::kMaxIters)
+      why = strfmt("--stream-iters: 1..%d messages, got %d", StreamLayout::kMaxIters, cfg->stream_iters);
+    for (size_t b : cfg->stream_sizes) {
+      if (!why.empty()) break;
+      why = stream_limits_error(cfg->stream_channels, cfg->stream_depth, b);
+      if (!why.empty()) why = "--stream-sizes / --stream-depth / --stream-channels: " + why;
+    }
+    if (!why.empty()) {
+      std::fprintf(stderr, "p2p_matrix: %s\n", why.c_str());
+      *exit_code = 1;
+      return false;
+    }
   }
   // --load needs a GPU to load, a quiet pass to compare with that is measured
   // the same way, and a results file that holds both passes of every run.
@@ -761,6 +815,9 @@ void run_latencies(const AppConfig& cfg, Transport& t, Bootstrap& boot, Buffers&
     if (cfg.device_latency)
       res.ring_latency.push_back(run_device_ring_latency(t, boot, cfg.latency_bytes, laps, std::min(laps, 20)));
   }
+  if (cfg.device_stream)
+    res.device_stream =
+        run_device_stream(t, boot, cfg.stream_sizes, cfg.stream_depth, cfg.stream_channels, cfg.stream_iters, cfg.dirs);
 }
 
 // Rank 0: the extended tables after the reference matrices, and the JSON /
@@ -790,6 +847,7 @@ void write_reports(const AppConfig& cfg, const Transport& t, const Bootstrap& bo
     print_latency(out, res.preposted_latency, n);
     print_latency(out, res.device_latency, n);
     for (const auto& rl : res.ring_latency) print_ring_latency(out, rl);
+    print_device_stream(out, res.device_stream);
     if (cfg.fuzz_rounds > 0)
       std::fprintf(out, "\n== fuzz: %d groups of random messages (1 B .. %s, random pairs incl. self): %s ==\n",
                    cfg.fuzz_rounds, format_size(fuzz_max).c_str(),
@@ -804,6 +862,7 @@ void write_reports(const AppConfig& cfg, const Transport& t, const Bootstrap& bo
     if (!res.preposted_latency.empty()) js << latency_to_json(res.preposted_latency, n) << "\n";
     if (!res.device_latency.empty()) js << latency_to_json(res.device_latency, n) << "\n";
     for (const auto& rl : res.ring_latency) js << ring_latency_to_json(rl) << "\n";
+    for (const auto& ds : res.device_stream) js << device_stream_to_json(ds) << "\n";
     if (cfg.fuzz_rounds > 0)
       js << strfmt("{\"type\":\"fuzz\",\"rounds\":%d,\"max_bytes\":%zu,\"mismatches\":%llu}", cfg.fuzz_rounds, fuzz_max,
                    static_cast<unsigned long long>(fuzz_bad))

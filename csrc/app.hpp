@@ -32,6 +32,11 @@ struct AppConfig {
   size_t target_bytes = 4ull << 30;
   bool latency = false;
   bool device_latency = false;   // ping-pong kernel matrix (one-sided transports)
+  bool device_stream = false;    // --device-stream: credit-flow ring kernel, message rate and bandwidth (one-sided transports)
+  std::vector<size_t> stream_sizes{16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536};  // 16:64K
+  int stream_depth = 8;          // messages in flight per channel
+  int stream_channels = 1;       // channels (sender / receiver wave pairs) per flow
+  int stream_iters = 2000;       // messages per channel and timed launch
   int latency_preposted = 0;     // > 0: ping-pong also posted in batches of this many behind a stream gate
   int fuzz_rounds = 0;           // --fuzz N: N groups of random verified messages (data-integrity stress)
   size_t latency_bytes = 8;
@@ -81,6 +86,7 @@ struct AppResult {
   std::vector<LatencyResult> device_latency;
   std::vector<LatencyResult> preposted_latency;
   std::vector<RingLatencyResult> ring_latency;  // --mode ring with --latency / --device-latency
+  std::vector<StreamResult> device_stream;      // --device-stream: one per (direction form, size)
   uint64_t mismatches = 0;
   int slow_flows = 0;  // flows under --min-gbs, or carried by the wrong transport (see count_slow_flows)
   // After the runs (collective): per pair (row-major n x n) the transport

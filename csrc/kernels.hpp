@@ -190,7 +190,47 @@ struct SignalArgs {
 };
 void launch_signal(const SignalArgs& args, hipStream_t stream);
 
-// ---- what both kernels spin on and count in (pingpong.hip) ----
+// ---- device-initiated stream (stream.hip) ----
+// The pipelined counterpart of the ping-pong: a channel is a one-directional
+// single-producer / single-consumer ring of `depth` slots of `bytes` in the
+// receiver's memory, with a `tail` flag beside it (messages published, written
+// by the sender) and a `head` flag in the sender's memory (messages consumed,
+// written by the receiver: the credit).  One role is one workgroup of one
+// wave; a launch carries up to kMaxStreamRoles of them by value.  Vector j of
+// the message with sequence s is the two 64-bit words {s, j}.  The sender
+// stamps stamps[0] before the first message, stamps[i + 1] after publishing
+// message i and stamps[iters + 1] after the final credit (it leaves only when
+// the ring is consumed); the receiver stamps stamps[i] when message i has
+// arrived.  status[0] bit 0 = a spin hit the deadline, status[1] = wrong 16 B
+// vectors among those the receiver checked (check_all: every one; otherwise
+// the first and, where there is more than one, the last of each message).
+struct StreamRole {
+  unsigned long long* out_flag;       // sender: peer's tail;  receiver: peer's head (credit)
+  const unsigned long long* in_flag;  // sender: own head;     receiver: own tail
+  unsigned char* ring;                // sender: peer's ring (written); receiver: own ring (read)
+  unsigned long long bytes;           // per message, multiple of 16, 16 .. 1 MiB
+  unsigned long long base;            // sequence base: message i carries seq = base + i + 1
+  int depth;                          // 1 .. 64, depth * bytes <= 4 MiB
+  int iters;                          // 1 .. 100000
+  int sender;                         // 1 = sender, 0 = receiver
+  int check_all;                      // receiver: 1 = every 16 B vector, 0 = first and last vector of each message
+  unsigned long long* stamps;         // sender: iters + 2 entries; receiver: iters entries
+  unsigned int* status;               // [0] bit 0 = deadline, [1] = wrong 16 B vectors
+  unsigned long long timeout_ticks;
+};
+constexpr int kMaxStreamRoles = 16;
+constexpr unsigned long long kMaxStreamBytes = 1ull << 20;      // per message
+constexpr unsigned long long kMaxStreamRingBytes = 4ull << 20;  // depth * bytes
+constexpr int kMaxStreamDepth = 64;
+constexpr int kMaxStreamIters = 100000;
+struct StreamArgs {
+  StreamRole role[kMaxStreamRoles];
+  int nroles;
+};
+// Checks every role's bounds and pointers (a P2P_CHECK each) before it launches.
+void launch_stream(const StreamRole* roles, int nroles, hipStream_t stream);
+
+// ---- what these kernels spin on and count in (pingpong.hip) ----
 // Memory for flags a wave spins on: uncached device memory when the runtime
 // allows it, so the spinning wave reads HBM rather than a stale line; plain
 // hipMalloc otherwise.  *uncached (if given) says which one it became.

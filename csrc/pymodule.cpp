@@ -36,6 +36,7 @@
 #include "runner.hpp"
 #include "routing.hpp"
 #include "schedule.hpp"
+#include "stream_layout.hpp"
 #include "transport.hpp"
 #include "units.hpp"
 
@@ -220,6 +221,20 @@ class Session {
 
   std::string device_latency(size_t bytes, int iters, int warmup) {
     return latency_to_json(run_device_latency(*t_, *boot_, bytes, iters, warmup), world());
+  }
+
+  // Device-initiated stream (runner.hpp run_device_stream): a JSON list, one
+  // {"device_stream": ...} object per (direction form, size).
+  std::string device_stream(const std::vector<size_t>& sizes, int depth, int channels, int iters, const std::string& dir) {
+    std::vector<Direction> dirs;
+    if (dir == "both")
+      dirs = {Direction::Uni, Direction::Bi};
+    else
+      dirs = {parse_direction(dir)};
+    std::string o = "[";
+    for (const StreamResult& r : run_device_stream(*t_, *boot_, sizes, depth, channels, iters, dirs))
+      o += (o.size() > 1 ? "," : "") + device_stream_to_json(r);
+    return o + "]";
   }
 
   // Dependent ring token chain (runner.hpp run_ring_latency); device=true
@@ -554,10 +569,9 @@ dev::SignalArgs signal_args(const FlagList& posts, const FlagList& waits, uintpt
   return a;
 }
 
-// A role is a dict of the PingRole fields (or what dict() accepts, or a
-// named tuple); base, in_base, leader and stamps default to 0, and only a
-// leader needs stamps.
-dev::PingRole ping_role_arg(const py::object& role) {
+// A role as a dict (a dict, what dict() accepts, or a named tuple) whose keys
+// are all among `fields`; `what` names the call in the error.
+py::dict role_dict(const py::object& role, const char* what, std::initializer_list<const char*> fields) {
   py::dict d;
   if (py::isinstance<py::dict>(role))
     d = role.cast<py::dict>();
@@ -565,21 +579,30 @@ dev::PingRole ping_role_arg(const py::object& role) {
     d = py::dict(role.attr("_asdict")());
   else
     d = py::dict(role);
-  static const char* const kFields[] = {"out_flag", "out_payload", "in_flag", "in_payload", "bytes",  "base",
-                                        "in_base",  "iters",       "leader",  "stamps",     "status", "timeout_ticks"};
   for (const auto& kv : d) {
     const std::string key = py::str(kv.first);
     bool known = false;
-    for (const char* f : kFields) known = known || key == f;
-    if (!known) throw py::value_error("pingpong: a role has no field '" + key + "'");
+    for (const char* f : fields) known = known || key == f;
+    if (!known) throw py::value_error(std::string(what) + ": a role has no field '" + key + "'");
   }
-  auto get = [&d](const char* key, bool required) -> uint64_t {
-    if (!d.contains(key)) {
-      if (required) throw py::value_error(strfmt("pingpong: a role needs '%s'", key));
-      return 0;
-    }
-    return d[key].cast<uint64_t>();
-  };
+  return d;
+}
+// Field `key` of such a dict as an unsigned integer; 0 where an optional one is absent.
+uint64_t role_field(const py::dict& d, const char* what, const char* key, bool required) {
+  if (!d.contains(key)) {
+    if (required) throw py::value_error(strfmt("%s: a role needs '%s'", what, key));
+    return 0;
+  }
+  return d[key].cast<uint64_t>();
+}
+
+// A role is a dict of the PingRole fields (role_dict);
+// base, in_base, leader and stamps default to 0, and only a
+// leader needs stamps.
+dev::PingRole ping_role_arg(const py::object& role) {
+  const py::dict d = role_dict(role, "pingpong", {"out_flag", "out_payload", "in_flag", "in_payload", "bytes", "base", "in_base",
+                                                  "iters", "leader", "stamps", "status", "timeout_ticks"});
+  auto get = [&d](const char* key, bool required) { return role_field(d, "pingpong", key, required); };
   dev::PingRole r{};
   r.bytes = get("bytes", true);
   if (r.bytes < 16 || r.bytes % 16) throw py::value_error("pingpong: bytes must be a multiple of 16, at least 16");
@@ -599,6 +622,79 @@ dev::PingRole ping_role_arg(const py::object& role) {
   if (r.leader || stamps) pointer_arg(stamps, 8, "pingpong: stamps");
   r.stamps = reinterpret_cast<unsigned long long*>(stamps);
   return r;
+}
+
+// A role is a dict of the StreamRole fields; base, sender and check_all
+// default to 0.
+dev::StreamRole stream_role_arg(const py::object& role) {
+  const py::dict d = role_dict(role, "stream", {"out_flag", "in_flag", "ring", "bytes", "base", "depth", "iters", "sender",
+                                                "check_all", "stamps", "status", "timeout_ticks"});
+  auto get = [&d](const char* key, bool required) { return role_field(d, "stream", key, required); };
+  dev::StreamRole r{};
+  r.bytes = get("bytes", true);
+  if (r.bytes < 16 || r.bytes % 16 || r.bytes > dev::kMaxStreamBytes)
+    throw py::value_error("stream: bytes must be a multiple of 16, 16 .. 1 MiB");
+  const uint64_t depth = get("depth", true), iters = get("iters", true);
+  if (depth < 1 || depth > static_cast<uint64_t>(dev::kMaxStreamDepth)) throw py::value_error("stream: depth must be 1 .. 64");
+  if (depth * r.bytes > dev::kMaxStreamRingBytes) throw py::value_error("stream: depth x bytes is at most 4 MiB");
+  if (iters < 1 || iters > static_cast<uint64_t>(dev::kMaxStreamIters)) throw py::value_error("stream: iters must be 1 .. 100000");
+  r.depth = static_cast<int>(depth);
+  r.iters = static_cast<int>(iters);
+  r.sender = get("sender", false) ? 1 : 0;
+  r.check_all = get("check_all", false) ? 1 : 0;
+  r.base = get("base", false);
+  r.timeout_ticks = get("timeout_ticks", true);
+  r.out_flag = reinterpret_cast<unsigned long long*>(pointer_arg(get("out_flag", true), 8, "stream: out_flag"));
+  r.in_flag = reinterpret_cast<const unsigned long long*>(pointer_arg(get("in_flag", true), 8, "stream: in_flag"));
+  r.ring = reinterpret_cast<unsigned char*>(pointer_arg(get("ring", true), 16, "stream: ring"));
+  r.stamps = reinterpret_cast<unsigned long long*>(pointer_arg(get("stamps", true), 8, "stream: stamps"));
+  r.status = reinterpret_cast<unsigned int*>(pointer_arg(get("status", true), 4, "stream: status"));
+  return r;
+}
+
+// stream_layout.hpp as a dict: the sizes, and every region as (name, offset,
+// bytes): "tail r.c" and "ring r.c" per source and channel, then "credit";
+// "head" lists the credit lines' offsets per destination and channel.
+py::dict stream_layout_py(int n, int channels, int depth, size_t bytes) {
+  StreamLayout l;
+  try {
+    l = stream_layout(n, channels, depth, bytes);
+  } catch (const Error& e) {
+    throw py::value_error(e.what());
+  }
+  py::list regions, tails, rings, heads;
+  for (int r = 0; r <= n; ++r) {
+    py::list tr, rr, hr;
+    for (int c = 0; c < channels; ++c) {
+      regions.append(py::make_tuple(strfmt("tail %d.%d", r, c), l.tail(r, c), StreamLayout::kHeader));
+      regions.append(py::make_tuple(strfmt("ring %d.%d", r, c), l.ring(r, c), l.ring_bytes));
+      tr.append(l.tail(r, c));
+      rr.append(l.ring(r, c));
+      hr.append(l.head(r, c));
+    }
+    tails.append(tr);
+    rings.append(rr);
+    heads.append(hr);
+  }
+  regions.append(py::make_tuple("credit", l.credit_offset, l.credit_bytes));
+  py::dict d;
+  d["n"] = l.n;
+  d["channels"] = l.channels;
+  d["depth"] = l.depth;
+  d["bytes"] = l.bytes;
+  d["ring_bytes"] = l.ring_bytes;
+  d["header_bytes"] = StreamLayout::kHeader;
+  d["credit_line"] = StreamLayout::kCreditLine;
+  d["credit_offset"] = l.credit_offset;
+  d["credit_bytes"] = l.credit_bytes;
+  d["total"] = l.total;
+  d["cap"] = StreamLayout::kPageCap;
+  d["self_slot"] = l.n;
+  d["regions"] = regions;
+  d["tail"] = tails;
+  d["ring"] = rings;
+  d["head"] = heads;
+  return d;
 }
 
 void launched(const char* what) {
@@ -778,6 +874,11 @@ PYBIND11_MODULE(_p2pcore, m) {
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("device_latency", &Session::device_latency, py::arg("bytes") = 8, py::arg("iters") = 1000,
            py::arg("warmup") = 100, py::call_guard<NativeCall, py::gil_scoped_release>())
+      .def("device_stream", &Session::device_stream, py::arg("sizes"), py::arg("depth") = 8, py::arg("channels") = 1,
+           py::arg("iters") = 2000, py::arg("dir") = "uni", py::call_guard<NativeCall, py::gil_scoped_release>(),
+           "Device-initiated stream (collective; one-sided transports): per flow `channels` credit-flow rings of `depth` "
+           "slots, one sender and one receiver wave each.  dir uni | bi | both.  JSON list, one device_stream object per "
+           "(direction form, size).")
       .def("latency", &Session::latency, py::arg("bytes") = 8, py::arg("iters") = 1000, py::arg("warmup") = 100,
            py::arg("preposted") = 0, py::call_guard<NativeCall, py::gil_scoped_release>(),
            "Ping-pong matrix (collective).  preposted=B: exchanges posted B at a time behind a stream gate and "
@@ -975,6 +1076,22 @@ PYBIND11_MODULE(_p2pcore, m) {
       "The ping-pong kernel (launch only): role a as one wave, or a and b as the two waves of one workgroup.  A role "
       "is a dict of out_flag, out_payload, in_flag, in_payload, bytes, base, in_base, iters, leader, stamps, status, "
       "timeout_ticks (pointers as integers).");
+  m.attr("MAX_STREAM_ROLES") = dev::kMaxStreamRoles;
+  m.def("stream", [](const std::vector<py::object>& roles, uintptr_t stream) {
+        if (roles.empty() || roles.size() > static_cast<size_t>(dev::kMaxStreamRoles))
+          throw py::value_error(strfmt("stream: 1 .. %d roles per launch", dev::kMaxStreamRoles));
+        std::vector<dev::StreamRole> v;
+        for (const py::object& r : roles) v.push_back(stream_role_arg(r));
+        dev::launch_stream(v.data(), static_cast<int>(v.size()), as_stream(stream));
+        launched("stream");
+      }, py::arg("roles"), py::arg("stream") = 0,
+      "The device-initiated stream kernel (launch only): up to MAX_STREAM_ROLES roles, one workgroup of one wave each.  "
+      "A role is a dict of out_flag, in_flag, ring, bytes, base, depth, iters, sender, check_all, stamps, status, "
+      "timeout_ticks (pointers as integers).");
+  m.def("stream_layout", &stream_layout_py, py::arg("n"), py::arg("channels"), py::arg("depth"), py::arg("bytes"),
+        "Where the device stream keeps its rings and flags in a rank's page (host code, no GPU): sizes, every region as "
+        "(name, offset, bytes), and the tail / ring / head offsets per rank slot (n: the self path) and channel.  "
+        "ValueError names the limit an argument breaks.");
   m.def("load_mfma", [](int wgs, uint32_t reps, uint64_t seed, uintptr_t out_ptr, uintptr_t stream, uintptr_t cancel_ptr,
                         uintptr_t done_ptr, uintptr_t tickets_ptr, uint64_t ordinal) {
         if (wgs < 1) throw py::value_error("load_mfma: wgs must be at least 1");

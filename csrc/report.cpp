@@ -480,6 +480,67 @@ void print_ring_latency(FILE* out, const RingLatencyResult& r) {
   std::fflush(out);
 }
 
+std::string device_stream_to_json(const StreamResult& r) {
+  // Rates and spans keep nine digits: gbs x 1e9 x span_s is the byte count again.
+  auto fine = [](double v) { return std::isfinite(v) ? strfmt("%.9g", v) : std::string("null"); };
+  std::ostringstream o;
+  uint64_t wrong = 0;
+  for (const auto& c : r.cells) wrong += c.wrong_vectors;
+  o << "{\"device_stream\":{\"form\":\"" << r.form << "\",\"bytes\":" << r.bytes << ",\"depth\":" << r.depth
+    << ",\"channels\":" << r.channels << ",\"iters\":" << r.iters << ",\"verify_iters\":" << r.verify_iters
+    << ",\"nranks\":" << r.nranks << ",\"wrong_vectors\":" << wrong << ",\"cells\":[";
+  for (size_t i = 0; i < r.cells.size(); ++i) {
+    const StreamCell& c = r.cells[i];
+    o << (i ? "," : "") << "{\"src\":" << c.src << ",\"dst\":" << c.dst << ",\"gbs\":" << fine(c.gbs)
+      << ",\"mmsgs\":" << fine(c.mmsgs) << ",\"span_s\":" << fine(c.span_s) << ",\"wall_s\":" << fine(c.wall_s)
+      << ",\"gap_us\":" << summary_json(c.gap_us) << ",\"recv_gbs\":" << fine(c.recv_gbs)
+      << ",\"recv_span_s\":" << fine(c.recv_span_s) << ",\"checked_vectors\":" << c.checked_vectors
+      << ",\"wrong_vectors\":" << c.wrong_vectors << "}";
+  }
+  o << "]}}";
+  return o.str();
+}
+
+void print_device_stream(FILE* out, const std::vector<StreamResult>& results) {
+  std::string form;
+  for (const StreamResult& r : results) {
+    if (r.cells.empty()) continue;
+    const int n = r.nranks;
+    if (r.form != form) {
+      form = r.form;
+      std::fprintf(out,
+                   "\n== device stream, %s: %d channel(s) of depth %d per flow, %d messages each (one sender and one "
+                   "receiver wave per channel, no host in the loop) ==\n",
+                   form == "bi" ? "both directions of a pair at once" : "one direction at a time", r.channels, r.depth,
+                   r.iters);
+      if (n <= 2)
+        std::fprintf(out, "  %9s %9s %10s %10s %11s %11s %10s\n", "size", "src->dst", "GB/s", "Mmsg/s", "gap p50 us",
+                     "gap p99 us", "recv GB/s");
+      else
+        std::fprintf(out, "  %9s %10s %10s %10s   (GB/s over the cells; matrices below)\n", "size", "min", "median", "max");
+    }
+    if (n <= 2) {
+      for (const StreamCell& c : r.cells)
+        std::fprintf(out, "  %9s %4d->%-3d %10.3f %10.3f %11.2f %11.2f %10.3f\n", format_size(r.bytes).c_str(), c.src, c.dst,
+                     c.gbs, c.mmsgs, c.gap_us.p50, c.gap_us.p99, c.recv_gbs);
+    } else {
+      std::vector<double> v;
+      for (const StreamCell& c : r.cells) v.push_back(c.gbs);
+      const Summary s = summarize(v);
+      std::fprintf(out, "  %9s %10.3f %10.3f %10.3f\n", format_size(r.bytes).c_str(), s.min, s.p50, s.max);
+    }
+  }
+  for (const StreamResult& r : results) {
+    if (r.nranks <= 2 || r.cells.empty()) continue;
+    std::vector<double> m(static_cast<size_t>(r.nranks) * r.nranks, 0.0);
+    for (const StreamCell& c : r.cells) m[static_cast<size_t>(c.src) * r.nranks + c.dst] = c.gbs;
+    print_matrix(out, strfmt("device stream %s, %s messages: GB/s (row = sender, col = receiver)", r.form.c_str(),
+                             format_size(r.bytes).c_str()),
+                 m, r.nranks, "%9.3f", true);
+  }
+  std::fflush(out);
+}
+
 std::string chrome_trace(const std::vector<RunRecord>& runs, int n) {
   double t0 = 0;
   bool have = false;

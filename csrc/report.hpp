@@ -106,6 +106,14 @@ std::string latency_to_json(const std::vector<LatencyResult>& lat, int n);
 // {"type":"ring_latency","method":...,"nranks":N,"bytes":B,"laps":L,"hop_us":{...},"lap_us":{...}}
 std::string ring_latency_to_json(const RingLatencyResult& r);
 void print_ring_latency(FILE* out, const RingLatencyResult& r);
+// --device-stream: one table per direction form.  Up to two ranks, a list with
+// one line per size and cell (GB/s, Mmsg/s, gap p50 / p99, recv GB/s); beyond,
+// a line per size (min / median / max GB/s over the cells) and its GB/s matrix.
+void print_device_stream(FILE* out, const std::vector<StreamResult>& results);
+// {"device_stream":{"form":"uni"|"bi","bytes":B,"depth":D,"channels":W,"iters":N,"verify_iters":V,"nranks":R,
+//   "wrong_vectors":0,"cells":[{"src":a,"dst":b,"gbs":..,"mmsgs":..,"span_s":..,"wall_s":..,"gap_us":{...},
+//   "recv_gbs":..,"recv_span_s":..,"checked_vectors":..,"wrong_vectors":0}]}}
+std::string device_stream_to_json(const StreamResult& r);
 
 // CSV rows: mode,dir,bytes,iters,timing,phase,src,dst,seconds,gbps,gbs,p50_us,p99_us,mismatches
 std::string csv_header();

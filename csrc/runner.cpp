@@ -1002,6 +1002,122 @@ std::vector<LatencyResult> run_device_latency(Transport& t, Bootstrap& boot, siz
   return out;
 }
 
+// ------------------------------------------------- device-initiated stream ----
+
+std::vector<StreamResult> run_device_stream(Transport& t, Bootstrap& boot, const std::vector<size_t>& sizes, int depth,
+                                            int channels, int iters, const std::vector<Direction>& dirs) {
+  P2P_CHECK(t.supports_device_stream(),
+            "device stream needs a one-sided transport (--transport ipc); " + t.name() + " has none");
+  P2P_CHECK(!sizes.empty() && !dirs.empty() && iters >= 1, "device stream: bad arguments");
+  const int n = boot.size(), me = boot.rank();
+  std::vector<size_t> sent_sizes;
+  for (size_t b : sizes) sent_sizes.push_back(std::max<size_t>(16, (b + 15) / 16 * 16));
+  t.stream_setup(channels, depth, *std::max_element(sent_sizes.begin(), sent_sizes.end()));
+  const int verify_iters = std::min(iters, kStreamVerifyIters);
+
+  // What one rank knows of a phase: its sender's times and its receiver's.
+  struct Part {
+    double span_s, wall_s, recv_span_s;
+    Summary gap_us;
+    uint64_t checked, wrong;
+  };
+  auto phase = [&](int send_to, int recv_from, size_t bytes) {
+    Part p{};
+    const bool active = send_to >= 0 || recv_from >= 0;
+    boot.barrier();  // the kernels of a cell start together (each spin has a deadline)
+    if (active) {
+      const auto v = t.device_stream(send_to, recv_from, bytes, verify_iters, true);
+      p.checked = v.checked_vectors;
+      p.wrong = v.wrong_vectors;
+    }
+    boot.barrier();
+    if (active) {
+      const double t0 = now_seconds();
+      const auto r = t.device_stream(send_to, recv_from, bytes, iters, false);
+      p.wall_s = now_seconds() - t0;
+      p.span_s = r.send_span_s;
+      p.recv_span_s = r.recv_span_s;
+      p.gap_us = summarize(r.gap_us);
+      p.wrong += r.wrong_vectors;
+    }
+    return boot.allgather_value(p);
+  };
+  auto cell = [&](int src, int dst, size_t bytes, const std::vector<Part>& all) {
+    const Part& s = all[static_cast<size_t>(src)];
+    const Part& r = all[static_cast<size_t>(dst)];
+    StreamCell c;
+    c.src = src;
+    c.dst = dst;
+    c.span_s = s.span_s;
+    c.wall_s = s.wall_s;
+    c.gap_us = s.gap_us;
+    const double msgs = static_cast<double>(channels) * iters;
+    if (c.span_s > 0) {
+      c.gbs = msgs * static_cast<double>(bytes) / c.span_s / 1e9;
+      c.mmsgs = msgs / c.span_s / 1e6;
+    }
+    c.recv_span_s = r.recv_span_s;
+    if (c.recv_span_s > 0)
+      c.recv_gbs = static_cast<double>(channels) * (iters - 1) * static_cast<double>(bytes) / c.recv_span_s / 1e9;
+    c.checked_vectors = r.checked;
+    c.wrong_vectors = r.wrong;
+    return c;
+  };
+
+  std::vector<StreamResult> out;
+  for (Direction d : dirs)
+    for (size_t b : sent_sizes) {
+      StreamResult r;
+      r.form = d == Direction::Bi ? "bi" : "uni";
+      r.bytes = b;
+      r.depth = depth;
+      r.channels = channels;
+      r.iters = iters;
+      r.verify_iters = verify_iters;
+      r.nranks = n;
+      out.push_back(r);
+    }
+  auto result = [&](size_t di, size_t si) -> StreamResult& { return out[di * sent_sizes.size() + si]; };
+
+  if (n == 1) {
+    for (size_t di = 0; di < dirs.size(); ++di)
+      for (size_t si = 0; si < sent_sizes.size(); ++si)
+        result(di, si).cells.push_back(cell(0, 0, sent_sizes[si], phase(0, 0, sent_sizes[si])));
+    return out;
+  }
+  for (const auto& round : round_robin_rounds(n)) {
+    int partner = -1;
+    bool first = false;  // this rank is the pair's first member
+    for (auto& pr : round) {
+      if (pr.first == me) partner = pr.second, first = true;
+      if (pr.second == me) partner = pr.first;
+    }
+    for (size_t di = 0; di < dirs.size(); ++di)
+      for (size_t si = 0; si < sent_sizes.size(); ++si) {
+        const size_t b = sent_sizes[si];
+        StreamResult& r = result(di, si);
+        if (dirs[di] == Direction::Bi) {
+          const auto all = phase(partner, partner, b);
+          for (auto& pr : round) {
+            r.cells.push_back(cell(pr.first, pr.second, b, all));
+            r.cells.push_back(cell(pr.second, pr.first, b, all));
+          }
+        } else {
+          // a -> b for every pair of the round, then b -> a.
+          const auto fwd = phase(partner >= 0 && first ? partner : -1, partner >= 0 && !first ? partner : -1, b);
+          for (auto& pr : round) r.cells.push_back(cell(pr.first, pr.second, b, fwd));
+          const auto back = phase(partner >= 0 && !first ? partner : -1, partner >= 0 && first ? partner : -1, b);
+          for (auto& pr : round) r.cells.push_back(cell(pr.second, pr.first, b, back));
+        }
+      }
+  }
+  for (auto& r : out)
+    std::sort(r.cells.begin(), r.cells.end(), [](const StreamCell& x, const StreamCell& y) {
+      return x.src != y.src ? x.src < y.src : x.dst < y.dst;
+    });
+  return out;
+}
+
 // ------------------------------------------------------ ring token chain ----
 
 namespace {

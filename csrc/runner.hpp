@@ -285,6 +285,44 @@ std::vector<LatencyResult> run_latency(Transport& t, Bootstrap& boot, size_t byt
 // run_latency; payloads are rounded up to 16 bytes (at most 64 KiB).
 std::vector<LatencyResult> run_device_latency(Transport& t, Bootstrap& boot, size_t bytes, int iters, int warmup);
 
+// ---- device-initiated stream: pipelined message rate and bandwidth ----
+// The streaming counterpart of the device ping-pong (Transport::device_stream;
+// the IPC transport): per channel a credit-flow ring of `depth` slots in the
+// receiver's memory, one sender wave and one receiver wave, no host in the
+// loop.  One cell is one ordered pair at one message size in one direction
+// form: "uni" measures a -> b and then b -> a, one at a time; "bi" both at
+// once.  Every cell is a barrier, a verification launch of min(iters, 256)
+// messages whose every 16-byte vector is compared, a barrier, and the timed
+// launch (first and last vector of each message compared).
+struct StreamCell {
+  int src = -1, dst = -1;
+  // The sender's clock: its first stamp to its last final credit over the
+  // channels, channels x iters messages.
+  double span_s = 0;
+  double gbs = 0;         // channels x iters x bytes / span_s / 1e9
+  double mmsgs = 0;       // channels x iters / span_s / 1e6
+  Summary gap_us;         // channel 0: from one published message to the next
+  // The receiver's own clock: first to last arrival over the channels,
+  // channels x (iters - 1) messages.  Never subtracted from the sender's.
+  double recv_span_s = 0;
+  double recv_gbs = 0;
+  double wall_s = 0;      // the sender's host clock around the timed call
+  uint64_t checked_vectors = 0;  // the verification launch: vectors compared (every one of every message)
+  uint64_t wrong_vectors = 0;    // of those and of the timed launch's, wrong (the transport makes any fatal)
+};
+struct StreamResult {
+  std::string form;  // "uni" | "bi"
+  size_t bytes = 0;  // as sent: rounded up to 16
+  int depth = 0, channels = 0, iters = 0, verify_iters = 0, nranks = 0;
+  std::vector<StreamCell> cells;  // sorted by (src, dst)
+};
+constexpr int kStreamVerifyIters = 256;
+// Walks round_robin_rounds(n) as run_device_latency does (n == 1: the self
+// cell, one launch carrying senders and receivers, the same under either
+// form).  Collective.  One result per (form, size), forms in the order given.
+std::vector<StreamResult> run_device_stream(Transport& t, Bootstrap& boot, const std::vector<size_t>& sizes, int depth,
+                                            int channels, int iters, const std::vector<Direction>& dirs);
+
 // ---- ring token chain: pipeline-parallel hop latency ----
 // Rank 0 sends a small message to rank 1; every rank forwards it to its
 // successor only after it has arrived from its predecessor (0 -> 1 -> ... ->

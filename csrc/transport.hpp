@@ -205,6 +205,31 @@ class Transport {
     return {};
   }
 
+  // ---- device-initiated stream (one-sided transports) ----
+  // The pipelined counterpart of the ping-pong: per channel a credit-flow ring
+  // of `depth` slots in the receiver's memory, driven entirely from the device
+  // (stream.hip).  stream_setup() is collective (every rank, same arguments).
+  // Then the sender calls device_stream(send_to = peer, ...) while the
+  // receiver calls device_stream(recv_from = peer, ...) with the same bytes /
+  // iters; either peer may be -1, both may be given (a bidirectional pair),
+  // and both equal to rank() is the self path.  Blocking; one launch.  The
+  // two sides' times come from their own device clocks and are never
+  // subtracted from each other.
+  struct DeviceStreamTimes {
+    bool sent = false, received = false;
+    double send_span_s = 0;      // sender: first stamp before a message to the last final credit, over the channels
+    std::vector<double> gap_us;  // sender, channel 0: time from one published message to the next (iters values)
+    double recv_span_s = 0;      // receiver: first to last arrival over the channels (iters - 1 messages each)
+    uint64_t checked_vectors = 0;  // receiver: 16-byte vectors compared with what was due
+    uint64_t wrong_vectors = 0;    // of those, wrong (a non-zero count is fatal in the transport)
+  };
+  virtual bool supports_device_stream() const { return false; }
+  virtual void stream_setup(int /*channels*/, int /*depth*/, size_t /*max_bytes*/) {}
+  virtual DeviceStreamTimes device_stream(int /*send_to*/, int /*recv_from*/, size_t /*bytes*/, int /*iters*/,
+                                          bool /*check_all*/) {
+    return {};
+  }
+
   // ---- stream gate (pre-posted latency, run_latency with preposted > 0) ----
   // gate_arm() enqueues a one-wave kernel that holds the stream carrying
   // small messages until gate_release() (or `timeout_s`); what is posted in

@@ -59,6 +59,7 @@
 #include "ipc_blocks.hpp"
 #include "ipc_peer_map.hpp"
 #include "ipc_pingpong.hpp"
+#include "ipc_stream.hpp"
 #include "kernels.hpp"
 #include "push_plan.hpp"
 #include "routing.hpp"
@@ -94,7 +95,9 @@ class IpcTransport final : public GpuTransport {
                            rank_, blocks, size);
             }),
         ping_(boot, stream_, [this] { sync(); }, timeout_, tick_hz_,
-              [this](size_t bytes, IpcHandle* handle) { return signal_page(bytes, handle); }) {
+              [this](size_t bytes, IpcHandle* handle) { return signal_page(bytes, handle); }),
+        dstream_(boot, stream_, [this] { sync(); }, timeout_, tick_hz_,
+                 [this](size_t bytes, IpcHandle* handle) { return signal_page(bytes, handle); }) {
     P2P_CHECK(engine_ == "kernel" || engine_ == "sdma" || engine_ == "push" || relay_,
               "ipc engine must be 'kernel', 'sdma', 'push' or 'relay'");
     static_assert(kPushMaxSignals == dev::kMaxSignals, "the planner cuts signals to what one launch carries");
@@ -119,6 +122,7 @@ class IpcTransport final : public GpuTransport {
     for (auto& r : regs_) close_registration(r);
     regs_.clear();
     ping_.release();
+    dstream_.release();
     release_sync_pages();
     blocks_.drain();
     destroy_graphs();
@@ -274,6 +278,12 @@ class IpcTransport final : public GpuTransport {
   }
   std::vector<double> device_ring_token(int pred, int succ, bool leader, size_t bytes, int laps) override {
     return ping_.ring_token(pred, succ, leader, bytes, laps);
+  }
+
+  bool supports_device_stream() const override { return true; }
+  void stream_setup(int channels, int depth, size_t max_bytes) override { dstream_.setup(channels, depth, max_bytes); }
+  DeviceStreamTimes device_stream(int send_to, int recv_from, size_t bytes, int iters, bool check_all) override {
+    return dstream_.stream(send_to, recv_from, bytes, iters, check_all);
   }
 
   // A finished stream still has to pass the rendezvous status word.
@@ -536,6 +546,7 @@ class IpcTransport final : public GpuTransport {
   IpcBlocks blocks_;
   std::vector<Registration> regs_;
   DevicePingPong ping_;
+  DeviceStream dstream_;
 
   // The open group, for every data mover.
   bool in_group_ = false;
