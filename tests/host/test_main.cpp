@@ -31,6 +31,8 @@
 #include "runner.hpp"
 #include "schedule.hpp"
 #include "stats.hpp"
+#include "stream_layout.hpp"
+#include "stream_plan.hpp"
 #include "transport.hpp"
 #include "units.hpp"
 
@@ -2850,6 +2852,767 @@ TEST(test_ipc_blocks_unknown_pointers) {
   EXPECT(mem.frees == 0 && blocks.pooled_bytes() == (size_t{2} << 20));
   blocks.drain();
   EXPECT(mem.frees == 1 && mem.live.empty());
+}
+
+// ------------------------- T0d: the device stream between kernel and report ----
+//
+// The kernel of the device-initiated stream has its own GPU tests.  What lies
+// between it and the numbers a user reads is host code: run_device_stream
+// (who sends to whom, which call a cell's numbers come from), StreamPlanner
+// (whose page, which slot and line, which sequence base) and
+// fold_stream_stamps (what the raw stamps mean).  Three tests:
+//   b  run_device_stream over a transport whose device_stream() is scripted:
+//      exact expected calls and cell values;
+//   a  the calls recorded there, planned by one StreamPlanner per rank and
+//      executed by a model of the kernel's protocol over fake pages;
+//   c  the fold over scripted stamps in a guarded scratch image.
+
+namespace {
+
+struct StreamCall {
+  int send_to, recv_from;
+  size_t bytes;
+  int iters;
+  bool check_all;
+  bool operator==(const StreamCall& o) const {
+    return send_to == o.send_to && recv_from == o.recv_from && bytes == o.bytes && iters == o.iters && check_all == o.check_all;
+  }
+};
+
+// What rank `rank` gets back from a call: a pure function of the rank and
+// the arguments, injective in them (the key), exact in a double, irregular.
+// A value taken from another rank, from the verification call instead of the
+// timed one, or from another size therefore differs.
+Transport::DeviceStreamTimes stream_script(int rank, const StreamCall& c, bool zero_spans = false) {
+  uint64_t key = static_cast<uint64_t>(rank);
+  key = key * 9 + static_cast<uint64_t>(c.send_to + 1);
+  key = key * 9 + static_cast<uint64_t>(c.recv_from + 1);
+  key = key * 2 + (c.check_all ? 1 : 0);
+  key = key * 512 + c.bytes / 16;
+  key = key * 512 + static_cast<uint64_t>(c.iters);
+  const double unit = 1.0 / static_cast<double>(uint64_t{1} << 36);
+  Transport::DeviceStreamTimes t;
+  t.sent = c.send_to >= 0;
+  t.received = c.recv_from >= 0;
+  if (t.sent) {
+    t.send_span_s = zero_spans ? 0.0 : static_cast<double>(3 * key + 1) * unit;
+    for (int i = 0; i < c.iters; ++i)
+      t.gap_us.push_back(static_cast<double>(1 + (key + 5 * static_cast<uint64_t>(i)) % 7 + static_cast<uint64_t>(i % 3)) / 8.0);
+  }
+  if (t.received) {
+    // One message has no span between a first and a last arrival.
+    t.recv_span_s = zero_spans || c.iters == 1 ? 0.0 : static_cast<double>(5 * key + 2) * unit;
+    t.checked_vectors = 7 + key % 100003;
+  }
+  return t;
+}
+
+// The host transport with a scripted device stream; `log` notes stream_setup
+// (S), the device_stream calls (v: check_all, t: timed) and, through
+// StreamCollectives, the barriers (b) and allgathers (a), in order.
+class ScriptedStream final : public Transport {
+ public:
+  explicit ScriptedStream(Transport& t, bool zero_spans = false) : t_(&t), zero_(zero_spans) {}
+  std::string name() const override { return "scripted-stream"; }
+  int rank() const override { return t_->rank(); }
+  int nranks() const override { return t_->nranks(); }
+  void* alloc(size_t b) override { return t_->alloc(b); }
+  void release(void* p) override { t_->release(p); }
+  void fill(void* p, size_t b, uint64_t s) override { t_->fill(p, b, s); }
+  void zero(void* p, size_t b) override { t_->zero(p, b); }
+  VerifyResult verify(const void* p, size_t b, uint64_t s) override { return t_->verify(p, b, s); }
+  void group_begin() override { t_->group_begin(); }
+  void send(const void* p, size_t b, int peer) override { t_->send(p, b, peer); }
+  void recv(void* p, size_t b, int peer) override { t_->recv(p, b, peer); }
+  void group_end() override { t_->group_end(); }
+  int mark() override { return t_->mark(); }
+  double elapsed_ms(int a, int b) override { return t_->elapsed_ms(a, b); }
+  void clear_marks() override { t_->clear_marks(); }
+  void sync() override { t_->sync(); }
+  bool supports_device_stream() const override { return true; }
+  void stream_setup(int channels, int depth, size_t max_bytes) override {
+    setups.push_back({static_cast<size_t>(channels), static_cast<size_t>(depth), max_bytes});
+    log += 'S';
+  }
+  DeviceStreamTimes device_stream(int send_to, int recv_from, size_t bytes, int iters, bool check_all) override {
+    const StreamCall c{send_to, recv_from, bytes, iters, check_all};
+    calls.push_back(c);
+    log += check_all ? 'v' : 't';
+    return stream_script(rank(), c, zero_);
+  }
+
+  std::string log;
+  std::vector<std::array<size_t, 3>> setups;  // (channels, depth, max_bytes)
+  std::vector<StreamCall> calls;
+
+ private:
+  Transport* t_;
+  bool zero_;
+};
+
+class StreamCollectives final : public Bootstrap {
+ public:
+  StreamCollectives(Bootstrap& b, std::string* log) : b_(&b), log_(log) {}
+  int rank() const override { return b_->rank(); }
+  int size() const override { return b_->size(); }
+  void allgather(const void* mine, void* all, size_t bytes) override {
+    *log_ += 'a';
+    b_->allgather(mine, all, bytes);
+  }
+  void bcast(void* buf, size_t bytes, int root) override { b_->bcast(buf, bytes, root); }
+  void barrier() override {
+    *log_ += 'b';
+    b_->barrier();
+  }
+  void abort(int code) override { b_->abort(code); }
+  std::string name() const override { return b_->name(); }
+  void set_timeout(double s) override { b_->set_timeout(s); }
+
+ private:
+  Bootstrap* b_;
+  std::string* log_;
+};
+
+struct StreamRun {  // one rank's
+  std::vector<StreamResult> res;
+  std::string log;
+  std::vector<std::array<size_t, 3>> setups;
+  std::vector<StreamCall> calls;
+};
+
+std::vector<StreamRun> scripted_stream(int n, const std::vector<size_t>& sizes, int depth, int channels, int iters,
+                                       const std::vector<Direction>& dirs, bool zero_spans = false) {
+  std::vector<StreamRun> out(static_cast<size_t>(n));
+  run_ranks(n, [&](Bootstrap& b, Transport& host) {
+    ScriptedStream t(host, zero_spans);
+    StreamCollectives cb(b, &t.log);
+    StreamRun& r = out[static_cast<size_t>(b.rank())];
+    r.res = run_device_stream(t, cb, sizes, depth, channels, iters, dirs);
+    r.log = t.log;
+    r.setups = t.setups;
+    r.calls = t.calls;
+    b.barrier();
+  });
+  return out;
+}
+
+// What the contract of run_device_stream (runner.hpp) makes every rank do,
+// from round_robin_rounds alone: its calls, and its log.
+void expected_stream_calls(int n, const std::vector<size_t>& sent_sizes, int iters, const std::vector<Direction>& dirs,
+                           std::vector<std::vector<StreamCall>>* calls, std::vector<std::string>* logs) {
+  calls->assign(static_cast<size_t>(n), {});
+  logs->assign(static_cast<size_t>(n), "S");
+  const int viters = std::min(iters, 256);
+  // One phase: to[r] / from[r] are rank r's peers, -1 for none.
+  auto phase = [&](const std::vector<int>& to, const std::vector<int>& from, size_t bytes) {
+    for (int r = 0; r < n; ++r) {
+      const size_t k = static_cast<size_t>(r);
+      const bool active = to[k] >= 0 || from[k] >= 0;
+      if (active) {
+        (*calls)[k].push_back({to[k], from[k], bytes, viters, true});
+        (*calls)[k].push_back({to[k], from[k], bytes, iters, false});
+      }
+      (*logs)[k] += active ? "bvbta" : "bba";
+    }
+  };
+  if (n == 1) {
+    for (size_t di = 0; di < dirs.size(); ++di)
+      for (size_t b : sent_sizes) phase({0}, {0}, b);
+    return;
+  }
+  for (const auto& round : round_robin_rounds(n))
+    for (Direction d : dirs)
+      for (size_t b : sent_sizes) {
+        std::vector<int> none(static_cast<size_t>(n), -1), first_to = none, second_to = none, both = none;
+        for (const auto& pr : round) {
+          first_to[static_cast<size_t>(pr.first)] = pr.second;   // the first member sends
+          second_to[static_cast<size_t>(pr.second)] = pr.first;  // the second member sends
+          both[static_cast<size_t>(pr.first)] = pr.second;
+          both[static_cast<size_t>(pr.second)] = pr.first;
+        }
+        if (d == Direction::Bi) {
+          phase(both, both, b);
+        } else {
+          // Sender's `to` is the receiver's `from`: first -> second, then back.
+          std::vector<int> second_from = none, first_from = none;
+          for (const auto& pr : round) {
+            second_from[static_cast<size_t>(pr.second)] = pr.first;
+            first_from[static_cast<size_t>(pr.first)] = pr.second;
+          }
+          phase(first_to, second_from, b);
+          phase(second_to, first_from, b);
+        }
+      }
+}
+
+bool finite_and_zero(double v) { return std::isfinite(v) && v == 0.0; }
+
+// One scripted run checked from end to end.
+void check_scripted_stream(int n, const std::vector<size_t>& sizes, const std::vector<size_t>& sent_sizes, int depth,
+                           int channels, int iters, const std::vector<Direction>& dirs, bool zero_spans = false) {
+  const auto runs = scripted_stream(n, sizes, depth, channels, iters, dirs, zero_spans);
+  std::vector<std::vector<StreamCall>> want_calls;
+  std::vector<std::string> want_logs;
+  expected_stream_calls(n, sent_sizes, iters, dirs, &want_calls, &want_logs);
+  const int viters = std::min(iters, 256);
+  auto collectives = [](const std::string& log) {
+    std::string o;
+    for (char c : log)
+      if (c == 'a' || c == 'b') o += c;
+    return o;
+  };
+  for (int me = 0; me < n; ++me) {
+    const StreamRun& run = runs[static_cast<size_t>(me)];
+    // Setup: once, with the largest rounded size.
+    EXPECT(run.setups.size() == 1);
+    if (run.setups.size() == 1)
+      EXPECT((run.setups[0] == std::array<size_t, 3>{static_cast<size_t>(channels), static_cast<size_t>(depth),
+                                                    *std::max_element(sent_sizes.begin(), sent_sizes.end())}));
+    // Call order: the same collectives on every rank, the bye rank included;
+    // a verification call and a timed call per phase, between their barriers.
+    EXPECT(run.log == want_logs[static_cast<size_t>(me)]);
+    EXPECT(collectives(run.log) == collectives(runs[0].log));
+    EXPECT(run.calls == want_calls[static_cast<size_t>(me)]);
+
+    // Result shape.
+    EXPECT(run.res.size() == dirs.size() * sizes.size());
+    if (run.res.size() != dirs.size() * sizes.size()) continue;
+    std::vector<std::pair<int, int>> pairs;
+    for (int a = 0; a < n; ++a)
+      for (int b = 0; b < n; ++b)
+        if (n == 1 || a != b) pairs.emplace_back(a, b);  // ascending (src, dst)
+    for (size_t di = 0; di < dirs.size(); ++di)
+      for (size_t si = 0; si < sizes.size(); ++si) {
+        const StreamResult& r = run.res[di * sizes.size() + si];
+        const bool bi = dirs[di] == Direction::Bi;
+        const size_t bytes = sent_sizes[si];
+        EXPECT(r.form == (bi ? "bi" : "uni") && r.bytes == bytes);
+        EXPECT(r.depth == depth && r.channels == channels && r.iters == iters && r.verify_iters == viters && r.nranks == n);
+        EXPECT(r.cells.size() == pairs.size());
+        if (r.cells.size() != pairs.size()) continue;
+        for (size_t k = 0; k < pairs.size(); ++k) {
+          const StreamCell& c = r.cells[k];
+          const int src = pairs[k].first, dst = pairs[k].second;
+          EXPECT(c.src == src && c.dst == dst);
+          // The sender's and the receiver's calls of this cell's phase.
+          const bool both = bi || n == 1;
+          const StreamCall s_timed{dst, both ? dst : -1, bytes, iters, false};
+          const StreamCall r_timed{both ? src : -1, src, bytes, iters, false};
+          const StreamCall r_verify{both ? src : -1, src, bytes, viters, true};
+          const auto ts = stream_script(src, s_timed, zero_spans);
+          const auto tr = stream_script(dst, r_timed, zero_spans);
+          const auto vr = stream_script(dst, r_verify, zero_spans);
+          EXPECT(c.span_s == ts.send_span_s);
+          EXPECT(c.wall_s >= 0);
+          expect_summary(c.gap_us, ts.gap_us);
+          EXPECT(c.gap_us.n == static_cast<size_t>(iters));
+          EXPECT(c.recv_span_s == tr.recv_span_s);
+          EXPECT(c.checked_vectors == vr.checked_vectors);
+          EXPECT(c.wrong_vectors == 0);
+          // runner.hpp: channels x iters messages over the sender's span,
+          // channels x (iters - 1) over the receiver's.
+          const double msgs = static_cast<double>(channels) * iters;
+          if (ts.send_span_s > 0) {
+            EXPECT_REL(c.gbs, msgs * static_cast<double>(bytes) / ts.send_span_s / 1e9);
+            EXPECT_REL(c.mmsgs, msgs / ts.send_span_s / 1e6);
+            EXPECT(c.gbs > 0 && c.mmsgs > 0);
+          } else {
+            EXPECT(zero_spans && finite_and_zero(c.gbs) && finite_and_zero(c.mmsgs));
+          }
+          if (tr.recv_span_s > 0) {
+            EXPECT_REL(c.recv_gbs, static_cast<double>(channels) * (iters - 1) * static_cast<double>(bytes) / tr.recv_span_s / 1e9);
+            EXPECT(c.recv_gbs > 0);
+          } else {
+            EXPECT((zero_spans || iters == 1) && finite_and_zero(c.recv_gbs));
+          }
+        }
+      }
+  }
+}
+
+}  // namespace
+
+TEST(test_scripted_device_stream) {
+  const std::vector<size_t> sizes{16, 100, 4096}, sent{16, 112, 4096};
+  const std::vector<std::vector<Direction>> forms{{Direction::Uni}, {Direction::Bi}, {Direction::Uni, Direction::Bi}};
+  // The scripted values differ between a cell's sender and receiver and
+  // between the verification and the timed call, or nothing below could tell
+  // them apart.
+  {
+    const StreamCall timed{1, 1, 112, 300, false}, verify{1, 1, 112, 256, true};
+    EXPECT(stream_script(0, timed).send_span_s != stream_script(1, {0, 0, 112, 300, false}).send_span_s);
+    EXPECT(stream_script(0, timed).recv_span_s != stream_script(0, verify).recv_span_s);
+    EXPECT(stream_script(0, timed).checked_vectors != stream_script(0, verify).checked_vectors);
+    EXPECT(stream_script(0, timed).send_span_s != stream_script(0, timed).recv_span_s);
+  }
+  for (int n : {1, 2, 3, 4, 5})
+    for (const auto& dirs : forms)
+      for (int iters : {1, 3, 300}) check_scripted_stream(n, sizes, sent, n % 2 ? 8 : 3, 1 + n % 3, iters, dirs);
+  // The largest size is itself rounded; a zero span leaves zero rates.
+  check_scripted_stream(3, {100, 16}, {112, 16}, 8, 2, 20, forms[2]);
+  check_scripted_stream(2, sizes, sent, 8, 2, 20, forms[2], true);
+  check_scripted_stream(1, sizes, sent, 8, 2, 300, forms[2], true);
+}
+
+// ---- a. the planned roles of every rank, executed over fake pages ----
+
+namespace {
+
+// The launches of a recorded run: launch 2p is phase p's verification call,
+// 2p + 1 its timed call, each with the ranks that made one.  A call's phase
+// is the number of allgathers its rank has behind it.
+std::vector<std::vector<std::pair<int, StreamCall>>> stream_launches(const std::vector<StreamRun>& runs) {
+  std::vector<std::vector<std::pair<int, StreamCall>>> out;
+  for (size_t r = 0; r < runs.size(); ++r) {
+    size_t phase = 0, next = 0;
+    for (char c : runs[r].log) {
+      if (c == 'a') ++phase;
+      if (c != 'v' && c != 't') continue;
+      const size_t launch = 2 * phase + (c == 't' ? 1 : 0);
+      if (out.size() <= launch) out.resize(launch + 1);
+      out[launch].emplace_back(static_cast<int>(r), runs[r].calls[next++]);
+    }
+    EXPECT(next == runs[r].calls.size());
+  }
+  return out;
+}
+
+// A change to a planned role before it is executed (rank, launch, layout, role).
+using StreamMutation = std::function<void(int, size_t, const StreamLayout&, StreamRolePlan*)>;
+
+// A page is kept in 64-bit words; every offset the model uses is a byte
+// offset that launch() has seen to be a multiple of 8.
+uint64_t page_get64(const std::vector<uint64_t>& page, size_t at) { return page[at / 8]; }
+void page_put64(std::vector<uint64_t>* page, size_t at, uint64_t v) { (*page)[at / 8] = v; }
+
+// The kernel's protocol (stream.hip; StreamWave in
+// tests/test_kernels_stream_gpu.py) on one array of layout.total bytes per rank.
+struct StreamModel {
+  struct Wave {
+    int rank;
+    StreamRolePlan p;
+    int i = 0;
+    bool done = false;
+    uint64_t wrong = 0;
+  };
+  struct Write {
+    int page;
+    size_t begin, end;
+    size_t wave;
+  };
+
+  int n;
+  StreamLayout lay;
+  std::vector<std::vector<uint64_t>> pages;
+  std::vector<std::string> bad;  // "liveness: ...", "correctness:", "containment:", "exclusive:", "continuity:", "order:", "scratch:"
+
+  explicit StreamModel(int nranks) : n(nranks) {}
+  // As setup_once zeroes every page of a new geometry.
+  void reset(const StreamLayout& l) {
+    lay = l;
+    pages.assign(static_cast<size_t>(n), std::vector<uint64_t>(l.total / 8, 0));
+  }
+  void note(const char* kind, size_t launch, const Wave& w, const std::string& what) {
+    if (bad.size() < 50)
+      bad.push_back(strfmt("%s launch %zu rank %d %s %d channel %d: %s", kind, launch, w.rank, w.p.sender ? "to" : "from",
+                           w.p.peer, w.p.channel, what.c_str()));
+  }
+
+  // One message of a wave, if it can move.
+  bool step(Wave* w) {
+    const StreamRolePlan& p = w->p;
+    std::vector<uint64_t>& own = pages[static_cast<size_t>(w->rank)];
+    const uint64_t seq = p.base + static_cast<uint64_t>(w->i) + 1;
+    const size_t nvec = p.bytes / 16;
+    if (p.sender) {
+      if (w->i == p.iters) {  // leaves only when the ring is consumed
+        if (page_get64(own, p.in_flag) < p.base + static_cast<uint64_t>(p.iters)) return false;
+        w->done = true;
+        return true;
+      }
+      if (w->i >= p.depth && page_get64(own, p.in_flag) < seq - static_cast<uint64_t>(p.depth)) return false;
+      std::vector<uint64_t>& ring = pages[static_cast<size_t>(p.ring_rank)];
+      const size_t slot = p.ring + static_cast<size_t>(w->i % p.depth) * p.bytes;
+      for (size_t j = 0; j < nvec; ++j) {
+        page_put64(&ring, slot + 16 * j, seq);
+        page_put64(&ring, slot + 16 * j + 8, j);
+      }
+      page_put64(&pages[static_cast<size_t>(p.out_rank)], p.out_flag, seq);
+    } else {
+      if (w->i == p.iters) {
+        w->done = true;
+        return true;
+      }
+      if (page_get64(own, p.in_flag) < seq) return false;
+      const std::vector<uint64_t>& ring = pages[static_cast<size_t>(p.ring_rank)];
+      const size_t slot = p.ring + static_cast<size_t>(w->i % p.depth) * p.bytes;
+      for (size_t j = 0; j < nvec; ++j)  // every vector, whatever the role's check mode
+        if (page_get64(ring, slot + 16 * j) != seq || page_get64(ring, slot + 16 * j + 8) != j) ++w->wrong;
+      page_put64(&pages[static_cast<size_t>(p.out_rank)], p.out_flag, seq);
+    }
+    ++w->i;
+    return true;
+  }
+
+  // One launch: the planned roles of every rank that called.
+  void launch(size_t index, std::vector<Wave> waves) {
+    std::vector<Write> writes;
+    bool runnable = true;
+    for (size_t k = 0; k < waves.size(); ++k) {
+      const Wave& w = waves[k];
+      const StreamRolePlan& p = w.p;
+      const int c = p.channel;
+      const bool self = p.peer == w.rank;
+      const size_t ring_end = p.ring + static_cast<size_t>(std::min(p.iters, p.depth)) * p.bytes;
+      // Inside the pages at all, or nothing below may touch them.
+      if (p.out_rank < 0 || p.out_rank >= n || p.ring_rank < 0 || p.ring_rank >= n || p.out_flag + 8 > lay.total ||
+          p.in_flag + 8 > lay.total || ring_end > lay.total || p.depth < 1 || p.bytes < 16 || p.bytes % 16 || p.out_flag % 8 ||
+          p.in_flag % 8 || p.ring % 16) {
+        note("containment:", index, w, "outside every page, or misaligned");
+        runnable = false;
+        continue;
+      }
+      // Containment: the sender writes the ring and tail of its inbox slot in
+      // the receiver's page, the receiver the head line of its own rank in
+      // the sender's page; the self path has slot and line n.
+      if (p.sender) {
+        const int slot = self ? n : w.rank;
+        if (p.ring_rank != p.peer || p.ring < lay.ring(slot, c) || ring_end > lay.ring(slot, c) + lay.ring_bytes)
+          note("containment:", index, w, strfmt("ring at %zu of rank %d's page", p.ring, p.ring_rank));
+        if (p.out_rank != p.peer || p.out_flag != lay.tail(slot, c))
+          note("containment:", index, w, strfmt("tail at %zu of rank %d's page", p.out_flag, p.out_rank));
+        if (p.in_flag != lay.head(self ? n : p.peer, c)) note("containment:", index, w, strfmt("waits for the head at %zu", p.in_flag));
+        writes.push_back({p.ring_rank, p.ring, ring_end, k});
+      } else {
+        if (p.out_rank != p.peer || p.out_flag != lay.head(self ? n : w.rank, c))
+          note("containment:", index, w, strfmt("head at %zu of rank %d's page", p.out_flag, p.out_rank));
+        const int slot = self ? n : p.peer;
+        if (p.ring_rank != w.rank || p.ring != lay.ring(slot, c) || p.in_flag != lay.tail(slot, c))
+          note("containment:", index, w, strfmt("reads the ring at %zu, the tail at %zu", p.ring, p.in_flag));
+      }
+      writes.push_back({p.out_rank, p.out_flag, p.out_flag + 8, k});
+      // Continuity: nothing is ever reset, so the role counts on from what
+      // its two flag words hold.
+      const uint64_t in = page_get64(pages[static_cast<size_t>(w.rank)], p.in_flag);
+      const uint64_t outv = page_get64(pages[static_cast<size_t>(p.out_rank)], p.out_flag);
+      if (in != p.base || outv != p.base)
+        note("continuity:", index, w, strfmt("base %llu, its flags hold %llu and %llu", p.base, static_cast<unsigned long long>(in),
+                                             static_cast<unsigned long long>(outv)));
+    }
+    // Exclusivity: no byte has two writers in one launch.
+    std::sort(writes.begin(), writes.end(), [](const Write& a, const Write& b) {
+      return a.page != b.page ? a.page < b.page : a.begin < b.begin;
+    });
+    for (size_t k = 1; k < writes.size(); ++k)
+      if (writes[k].page == writes[k - 1].page && writes[k].begin < writes[k - 1].end)
+        note("exclusive:", index, waves[writes[k].wave],
+             strfmt("byte %zu of rank %d's page is also written by rank %d", writes[k].begin, writes[k].page,
+                    waves[writes[k - 1].wave].rank));
+    // One rank's roles: receivers first, then senders, channels ascending;
+    // status blocks and stamp regions share no 256-byte block and fit the
+    // scratch of that many roles.
+    for (size_t k = 0; k < waves.size(); ++k) {
+      size_t first = k, count = 0;
+      while (first > 0 && waves[first - 1].rank == waves[k].rank) --first;
+      while (first + count < waves.size() && waves[first + count].rank == waves[k].rank) ++count;
+      const StreamRolePlan& p = waves[k].p;
+      const size_t pos = k - first;
+      if (pos > 0) {
+        const StreamRolePlan& q = waves[k - 1].p;
+        if ((p.sender == q.sender && p.channel != q.channel + 1) || (p.sender != q.sender && (q.sender || p.channel != 0)))
+          note("order:", index, waves[k], "receivers first, then senders, channels ascending");
+        const size_t q_end = q.stamps + 8 * (static_cast<size_t>(q.iters) + 2);
+        if (p.status != q.status + 256 || p.stamps % 256 || (q_end + 255) / 256 * 256 > p.stamps)
+          note("scratch:", index, waves[k], "a status block or stamp region shares a 256-byte block with its neighbour's");
+      } else if (p.status != 0 || p.stamps != 256 * 16) {
+        note("scratch:", index, waves[k], "the first role's status block and stamps");
+      }
+      if (p.stamps + 8 * (static_cast<size_t>(p.iters) + 2) > StreamScratch::used(count, p.iters) || count > 16)
+        note("scratch:", index, waves[k], "beyond what the launch copies back");
+    }
+    if (!runnable) return;
+    // Round-robin, one message of each role a turn, until none can move.
+    for (bool moved = true; moved;) {
+      moved = false;
+      for (Wave& w : waves)
+        if (!w.done && step(&w)) moved = true;
+    }
+    for (const Wave& w : waves) {
+      if (!w.done) note("liveness:", index, w, strfmt("waits at message %d of %d", w.i, w.p.iters));
+      if (w.wrong) note("correctness:", index, w, strfmt("%llu wrong vectors", static_cast<unsigned long long>(w.wrong)));
+    }
+  }
+};
+
+// A recorded run planned and executed under each geometry in turn, with the
+// same planners throughout: what a second stream_setup() does in between is
+// reset() on every rank and zeroed pages.
+std::vector<std::string> stream_model_violations(const std::vector<StreamRun>& runs, const std::vector<StreamLayout>& geometries,
+                                                 const StreamMutation& mutate = nullptr) {
+  const int n = static_cast<int>(runs.size());
+  const auto launches = stream_launches(runs);
+  StreamModel model(n);
+  std::vector<StreamPlanner> planners;
+  for (int r = 0; r < n; ++r) planners.emplace_back(r, n);
+  for (const StreamLayout& lay : geometries) {
+    model.reset(lay);
+    for (StreamPlanner& p : planners) p.reset(lay);
+    for (size_t l = 0; l < launches.size(); ++l) {
+      std::vector<StreamModel::Wave> waves;
+      for (const auto& rc : launches[l]) {
+        const StreamCall& c = rc.second;
+        for (StreamRolePlan role : planners[static_cast<size_t>(rc.first)].plan(c.send_to, c.recv_from, c.bytes, c.iters, c.check_all)) {
+          if (mutate) mutate(rc.first, l, lay, &role);
+          StreamModel::Wave w;
+          w.rank = rc.first;
+          w.p = role;
+          waves.push_back(w);
+        }
+      }
+      model.launch(l, std::move(waves));
+    }
+  }
+  return model.bad;
+}
+
+bool has_violation(const std::vector<std::string>& bad, const char* kind) {
+  for (const auto& s : bad)
+    if (s.rfind(kind, 0) == 0) return true;
+  return false;
+}
+
+void expect_no_stream_violations(const std::vector<std::string>& bad, const std::string& what) {
+  EXPECT(bad.empty());
+  for (size_t i = 0; i < bad.size() && i < 5; ++i) std::fprintf(stderr, "    %s: %s\n", what.c_str(), bad[i].c_str());
+}
+
+const std::vector<Direction> kBothForms{Direction::Uni, Direction::Bi};
+
+}  // namespace
+
+TEST(test_stream_plan_against_ring_model) {
+  // 16, 112 and 4096 bytes in one run: the layout's slots are larger than
+  // most of the messages sent into them.
+  const std::vector<size_t> sizes{16, 100, 4096};
+  for (int n : {1, 2, 3, 4, 5, 8})
+    for (int depth : {1, 8})
+      for (int iters : {1, 3, 3 * depth + 1}) {
+        if (depth == 1 && iters == 3) continue;  // 3 * depth + 1 = 4 covers it
+        // Channels and depth only pass through run_device_stream: one
+        // recording serves both channel counts.
+        const auto runs = scripted_stream(n, sizes, depth, 1, iters, kBothForms);
+        for (int channels : {1, 8}) {
+          // Then laid out again, as a second stream_setup with other arguments does.
+          const std::vector<StreamLayout> geometries{stream_layout(n, channels, depth, 4096),
+                                                     stream_layout(n, channels == 1 ? 2 : 3, depth + 2, 4112)};
+          expect_no_stream_violations(stream_model_violations(runs, geometries),
+                                      strfmt("n %d depth %d iters %d channels %d", n, depth, iters, channels));
+        }
+      }
+}
+
+// The model has teeth: each of these one-line changes to the planned roles
+// breaks the contract, and the model must say so.
+TEST(test_stream_model_rejects_mutations) {
+  const std::vector<size_t> sizes{16, 100};
+  // 300 messages: the verification launch sends 256 of them, the timed one 300.
+  const int depth = 8, channels = 2, iters = 300;
+  const auto self = scripted_stream(1, sizes, depth, channels, iters, kBothForms);
+  const auto three = scripted_stream(3, sizes, depth, channels, iters, kBothForms);
+  const std::vector<StreamLayout> lay1{stream_layout(1, channels, depth, 112)}, lay3{stream_layout(3, channels, depth, 112)};
+  EXPECT(stream_model_violations(self, lay1).empty() && stream_model_violations(three, lay3).empty());
+  {  // the self path in slot `rank` instead of slot n
+    const auto bad = stream_model_violations(self, lay1, [](int rank, size_t, const StreamLayout& l, StreamRolePlan* r) {
+      (r->sender ? r->out_flag : r->in_flag) = l.tail(rank, r->channel);
+      r->ring = l.ring(rank, r->channel);
+    });
+    EXPECT(has_violation(bad, "containment:"));
+  }
+  {  // the receiver's credit on line recv_from instead of its own rank
+    const auto bad = stream_model_violations(three, lay3, [](int, size_t, const StreamLayout& l, StreamRolePlan* r) {
+      if (!r->sender) r->out_flag = l.head(r->peer, r->channel);
+    });
+    EXPECT(has_violation(bad, "containment:") && has_violation(bad, "liveness:"));
+  }
+  {  // the sender's ring in slot send_to instead of its own rank
+    const auto bad = stream_model_violations(three, lay3, [](int, size_t, const StreamLayout& l, StreamRolePlan* r) {
+      if (r->sender) r->ring = l.ring(r->peer, r->channel), r->out_flag = l.tail(r->peer, r->channel);
+    });
+    EXPECT(has_violation(bad, "containment:") && has_violation(bad, "liveness:"));
+  }
+  {  // a base not advanced after a launch: the timed launch starts where the verification did
+    const auto bad = stream_model_violations(three, lay3, [](int, size_t launch, const StreamLayout&, StreamRolePlan* r) {
+      if (launch % 2 == 1) r->base -= 256;
+    });
+    EXPECT(has_violation(bad, "continuity:"));
+  }
+  {  // a base advanced by verify_iters where the launch sent iters
+    const auto bad = stream_model_violations(three, lay3, [](int, size_t, const StreamLayout&, StreamRolePlan* r) {
+      r->base -= r->base / (256 + 300) * (300 - 256);
+    });
+    EXPECT(has_violation(bad, "continuity:"));
+  }
+  {  // the two channels of a flow share a head line
+    const auto bad = stream_model_violations(three, lay3, [](int, size_t, const StreamLayout&, StreamRolePlan* r) {
+      if (r->channel == 1) (r->sender ? r->in_flag : r->out_flag) -= StreamLayout::kCreditLine;
+    });
+    EXPECT(has_violation(bad, "exclusive:"));
+  }
+}
+
+TEST(test_stream_planner_refuses_bad_calls) {
+  StreamPlanner p(1, 3);
+  EXPECT(has_text(fatal_text([&] { p.plan(0, -1, 16, 1, false); }), "stream_setup() first"));
+  p.reset(stream_layout(3, 2, 4, 100));
+  EXPECT(has_text(fatal_text([&] { p.plan(3, -1, 16, 1, false); }), "bad peer"));
+  EXPECT(has_text(fatal_text([&] { p.plan(-1, -2, 16, 1, false); }), "bad peer"));
+  EXPECT(has_text(fatal_text([&] { p.plan(-1, -1, 16, 1, false); }), "nothing to send or receive"));
+  EXPECT(has_text(fatal_text([&] { p.plan(1, -1, 16, 1, false); }), "the self path sends to and receives from the own rank"));
+  EXPECT(has_text(fatal_text([&] { p.plan(1, 0, 16, 1, false); }), "the self path"));
+  EXPECT(has_text(fatal_text([&] { p.plan(0, -1, 16, 0, false); }), "1..100000 messages"));
+  EXPECT(has_text(fatal_text([&] { p.plan(0, -1, 16, 100001, false); }), "1..100000 messages"));
+  EXPECT(has_text(fatal_text([&] { p.plan(0, -1, 113, 1, false); }), "messages of at most 112 bytes were set up"));
+  // A refused call counts nothing; an accepted one counts its messages on
+  // the lines it used only, and rounds its size up.
+  for (auto v : p.sent()) EXPECT(v == 0);
+  const auto roles = p.plan(0, 2, 100, 5, true);
+  EXPECT(roles.size() == 4 && roles[0].bytes == 112 && !roles[0].sender && roles[3].sender && roles[3].channel == 1);
+  EXPECT(p.sent() == (std::vector<unsigned long long>{5, 5, 0, 0, 0, 0, 0, 0}));
+  EXPECT(p.recvd() == (std::vector<unsigned long long>{0, 0, 0, 0, 5, 5, 0, 0}));
+  EXPECT(p.plan(1, 1, 16, 7, false)[0].base == 0 && p.plan(1, 1, 16, 1, false)[3].base == 7);
+  EXPECT(p.sent()[6] == 8 && p.recvd()[7] == 8);
+  p.reset(stream_layout(3, 1, 4, 100));
+  EXPECT(p.sent() == (std::vector<unsigned long long>{0, 0, 0, 0}) && p.plan(0, 2, 16, 5, true)[0].base == 0);
+}
+
+// ---- c. the fold over scripted stamps ----
+
+namespace {
+
+constexpr double kStreamHz = 100e6;
+
+// Role k's stamp i: exact integers, irregular steps, every role with its own
+// start.  Channel 0 (k % channels == 0) starts neither first nor last and
+// ends neither first nor last where there are four channels.
+uint64_t scripted_stamp(size_t k, size_t channels, size_t i) {
+  static const uint64_t start[4] = {500, 100, 900, 300};
+  uint64_t t = 1000000 + start[k % channels % 4] + 13 * (k / channels);
+  for (size_t j = 0; j < i; ++j) t += 3 + (7 * j + 5 * (k % channels) + (k / channels)) % 11;
+  return t;
+}
+
+constexpr unsigned char kGuard = 0xAB;
+
+// The scratch image a launch of `plan` leaves: exactly as many bytes as the
+// transport copies back (the ASan build sees any read beyond), guard bytes
+// wherever the kernel writes nothing (the padding of the status blocks, the
+// stamps a role does not write), status words clean.
+std::vector<unsigned char> scripted_scratch(const std::vector<StreamRolePlan>& plan, size_t channels, int iters) {
+  const size_t stride = (static_cast<size_t>(iters) + 2 + 31) / 32 * 32;  // entries: whole 256-byte blocks
+  std::vector<unsigned char> img(16 * 256 + plan.size() * stride * 8, kGuard);
+  for (size_t k = 0; k < plan.size(); ++k) {
+    EXPECT(plan[k].status == 256 * k && plan[k].stamps == 16 * 256 + k * stride * 8);
+    std::memset(img.data() + 256 * k, 0, 8);
+    const size_t written = plan[k].sender ? static_cast<size_t>(iters) + 2 : static_cast<size_t>(iters);
+    for (size_t i = 0; i < written; ++i) {
+      const uint64_t v = scripted_stamp(k, channels, i);
+      std::memcpy(img.data() + 16 * 256 + (k * stride + i) * 8, &v, 8);
+    }
+  }
+  return img;
+}
+
+}  // namespace
+
+TEST(test_stream_fold_scripted_stamps) {
+  EXPECT(StreamScratch::used(3, 30) == 16 * 256 + 3 * 32 * 8 && StreamScratch::used(3, 31) == 16 * 256 + 3 * 64 * 8);
+  const int n = 4, me = 0;
+  for (size_t channels : {size_t{1}, size_t{4}})
+    for (int iters : {1, 5, 31, 70})
+      for (size_t bytes : {size_t{16}, size_t{4096}})
+        for (bool check_all : {false, true})
+          for (int form = 0; form < 3; ++form) {  // sender and receiver, sender only, receiver only
+            const int send_to = form == 2 ? -1 : 1, recv_from = form == 1 ? -1 : 3;
+            StreamPlanner planner(me, n);
+            planner.reset(stream_layout(n, static_cast<int>(channels), 8, 4096));
+            const auto plan = planner.plan(send_to, recv_from, bytes, iters, check_all);
+            EXPECT(plan.size() == channels * (form == 0 ? 2 : 1));
+            const auto img = scripted_scratch(plan, channels, iters);
+            EXPECT(img.size() == StreamScratch::used(plan.size(), iters));
+            const StreamFold f = fold_stream_stamps(plan, img.data(), img.size(), kStreamHz);
+            EXPECT(f.ok() && f.role == -1 && !f.deadline && f.wrong == 0 && f.times.wrong_vectors == 0);
+            const auto& t = f.times;
+            EXPECT(t.sent == (send_to >= 0) && t.received == (recv_from >= 0));
+            // Expected values by plain loops over the script.
+            uint64_t s_min = ~0ull, s_max = 0, r_min = ~0ull, r_max = 0;
+            size_t s_min_k = 0, s_max_k = 0, r_min_k = 0, r_max_k = 0, first_sender = plan.size();
+            const size_t it = static_cast<size_t>(iters);
+            for (size_t k = 0; k < plan.size(); ++k) {
+              if (plan[k].sender) {
+                if (first_sender == plan.size()) first_sender = k;
+                if (scripted_stamp(k, channels, 0) < s_min) s_min = scripted_stamp(k, channels, 0), s_min_k = k;
+                if (scripted_stamp(k, channels, it + 1) > s_max) s_max = scripted_stamp(k, channels, it + 1), s_max_k = k;
+              } else {
+                if (scripted_stamp(k, channels, 0) < r_min) r_min = scripted_stamp(k, channels, 0), r_min_k = k;
+                if (scripted_stamp(k, channels, it - 1) > r_max) r_max = scripted_stamp(k, channels, it - 1), r_max_k = k;
+              }
+            }
+            if (channels == 4) {  // channel 0 decides neither end of either span
+              if (t.sent) EXPECT(plan[s_min_k].channel != 0 && plan[s_max_k].channel != 0);
+              if (t.received) EXPECT(plan[r_min_k].channel != 0 && plan[r_max_k].channel != 0);
+            }
+            if (t.sent) {
+              EXPECT(t.send_span_s == static_cast<double>(s_max - s_min) / kStreamHz && t.send_span_s > 0);
+              EXPECT(plan[first_sender].channel == 0);
+              EXPECT(t.gap_us.size() == it);
+              for (size_t i = 0; i < it && i < t.gap_us.size(); ++i)
+                EXPECT(t.gap_us[i] == static_cast<double>(scripted_stamp(first_sender, channels, i + 1) -
+                                                          scripted_stamp(first_sender, channels, i)) / kStreamHz * 1e6);
+            } else {
+              EXPECT(t.send_span_s == 0 && t.gap_us.empty());
+            }
+            if (t.received) {
+              EXPECT(t.recv_span_s == static_cast<double>(r_max - r_min) / kStreamHz);
+              EXPECT(iters > 1 || channels > 1 || t.recv_span_s == 0);
+              const uint64_t per_message = check_all ? bytes / 16 : (bytes == 16 ? 1 : 2);
+              EXPECT(t.checked_vectors == channels * it * per_message);
+            } else {
+              EXPECT(t.recv_span_s == 0 && t.checked_vectors == 0);
+            }
+
+            // A deadline bit, or a wrong count, in exactly one role's status
+            // block: that role is reported, with its direction and its peer.
+            for (size_t k = 0; k < plan.size(); ++k) {
+              auto late = img;
+              const unsigned int bit = 1;
+              std::memcpy(late.data() + 256 * k, &bit, 4);
+              const StreamFold d = fold_stream_stamps(plan, late.data(), late.size(), kStreamHz);
+              EXPECT(!d.ok() && d.role == static_cast<int>(k) && d.deadline && d.wrong == 0);
+              auto wrong = img;
+              const unsigned int count = 7 + static_cast<unsigned int>(k);
+              std::memcpy(wrong.data() + 256 * k + 4, &count, 4);
+              const StreamFold w = fold_stream_stamps(plan, wrong.data(), wrong.size(), kStreamHz);
+              EXPECT(!w.ok() && w.role == static_cast<int>(k) && !w.deadline && w.wrong == count &&
+                     w.times.wrong_vectors == count);
+              if (w.role == static_cast<int>(k)) {
+                const StreamRolePlan& r = plan[k];
+                const bool sender = k >= (form == 0 ? channels : 0) && form != 2;
+                EXPECT(r.sender == sender && r.peer == (sender ? 1 : 3) && r.channel == static_cast<int>(k % channels));
+              }
+              if (k + 1 < plan.size()) {  // two roles fail: the first in launch order is named
+                std::memcpy(wrong.data() + 256 * (k + 1), &bit, 4);
+                EXPECT(fold_stream_stamps(plan, wrong.data(), wrong.size(), kStreamHz).role == static_cast<int>(k));
+              }
+            }
+          }
+  // The fold reads no further than the image it is given.
+  StreamPlanner planner(0, 2);
+  planner.reset(stream_layout(2, 1, 8, 4096));
+  const auto plan = planner.plan(1, 1, 64, 40, false);
+  const auto img = scripted_scratch(plan, 1, 40);
+  EXPECT(has_text(fatal_text([&] { fold_stream_stamps(plan, img.data(), img.size() - 64 * 8 + 41 * 8, kStreamHz); }),
+                  "outside the scratch"));
+  EXPECT(fold_stream_stamps(plan, img.data(), img.size() - 64 * 8 + 42 * 8, kStreamHz).ok());
 }
 
 

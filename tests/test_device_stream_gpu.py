@@ -75,9 +75,10 @@ def check_records(recs, nranks, sizes, forms, channels, depth, iters, wall_s):
             assert c["gbs"] <= ROOF_GBS and c["recv_gbs"] <= ROOF_GBS, c
 
 
-@pytest.mark.parametrize("channels", [1, 4])
+@pytest.mark.parametrize("channels", [1, 4, 8])
 def test_self_cell(exe, tmp_path, channels):
-    """One process: senders and receivers of every channel in one launch."""
+    """One process: senders and receivers of every channel in one launch
+    (8 channels: 16 roles, as many as a launch carries)."""
     js = tmp_path / "r.json"
     t0 = time.perf_counter()
     out = subprocess.run([exe, "--transport", "ipc", "--mode", "self", "--size", "4K", "-n", "2", "--no-compat",
@@ -93,22 +94,31 @@ def test_self_cell(exe, tmp_path, channels):
 
 
 @pytest.mark.skipif(not os.path.exists(MPIRUN), reason="no mpirun")
-@pytest.mark.parametrize("nranks", [2, 4])
+@pytest.mark.parametrize("nranks", [2, 3, 4])
 def test_ranks_on_one_gpu(exe, tmp_path, nranks):
     """Several processes on one GPU stream into each other's pages: every
-    pair of every round, both directions, one at a time and both at once."""
+    pair of every round, both directions, one at a time and both at once.
+    With three ranks one of them sits out every round, and that run also asks
+    for messages of 100 bytes: they are sent, checked and reported as 112
+    bytes, 7 vectors each."""
     js = tmp_path / "r.json"
+    odd = nranks == 3
     t0 = time.perf_counter()
     out = subprocess.run([MPIRUN, "-n", str(nranks), exe, "--transport", "ipc", "--device", "0", "--mode", "ring",
                           "--size", "4K", "-n", "2", "--no-compat", "--dir", "both", "--device-stream", "--stream-sizes",
-                          "16,4K,64K", "--stream-iters", "200", "--stream-channels", "2", "--json", str(js), "--timeout",
+                          "16,100,4K,64K" if odd else "16,4K,64K", "--stream-iters", "200", "--stream-channels", "2",
+                          "--json", str(js), "--timeout",
                           "60"], capture_output=True, text=True, timeout=240)
     wall_s = time.perf_counter() - t0
     assert out.returncode == 0, out.stderr[-3000:]
     assert "== device stream, one direction at a time: 2 channel(s) of depth 8" in out.stdout
     if nranks > 2:
         assert "device stream bi, 64K messages: GB/s (row = sender, col = receiver)" in out.stdout
-    check_records(stream_records(js.read_text().splitlines()), nranks, [16, 4096, 65536], ["uni", "bi"], 2, 8, 200, wall_s)
+    recs = stream_records(js.read_text().splitlines())
+    check_records(recs, nranks, [16, 112, 4096, 65536] if odd else [16, 4096, 65536], ["uni", "bi"], 2, 8, 200, wall_s)
+    if odd:
+        assert all(c["checked_vectors"] == 200 * 7 * 2 for r in recs if r["bytes"] == 112 for c in r["cells"])
+        assert sum(r["bytes"] == 112 for r in recs) == 2
 
 
 def session_calls(nranks):

@@ -380,6 +380,28 @@ def test_credits_flow(native, hz, long, depth, nbytes, channels, kind):
     assert_flow_finished(mem, chans, bases, 2 * iters)
 
 
+LIMITS = [pytest.param(8, 1040, 2, id="16-roles"),            # MAX_STREAM_ROLES: 8 receivers and 8 senders
+          pytest.param(1, 1 << 20, 4, id="1MiB-4MiB-ring"),   # the largest message in the largest ring
+          pytest.param(1, 65536, 64, id="depth-64")]          # the deepest ring, again 4 MiB
+
+
+@pytest.mark.parametrize("kind", MEMORY)
+@pytest.mark.parametrize("channels,nbytes,depth", LIMITS)
+def test_credits_flow_at_the_limits(native, hz, channels, nbytes, depth, kind):
+    """test_credits_flow at the shapes the kernel's limits name (kernels.hpp:
+    16 roles a launch, 1 MiB a message, depth 64, a ring of 4 MiB), each ring
+    lapped three times: 3 x depth + 1 messages, then as many again."""
+    assert native.MAX_STREAM_ROLES == 2 * 8 and depth * nbytes <= 4 << 20
+    iters = 3 * depth + 1
+    bases = [2**32 + 5 + 1000 * c for c in range(channels)]
+    mem, chans = flow_memory(nbytes, depth, iters, channels, bases)
+    dev = Device(native, kind, mem)
+    launch_flow(native, hz, dev, mem, chans, bases, check_all=1)
+    assert_flow_finished(mem, chans, bases, iters)
+    launch_flow(native, hz, dev, mem, chans, [b + iters for b in bases], check_all=0)
+    assert_flow_finished(mem, chans, bases, 2 * iters)
+
+
 # --------------------------------------------------------- D. deadlines ----
 
 DEADLINE_S = 0.02
