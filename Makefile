@@ -26,7 +26,7 @@ HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
 CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o diagnose_hip.o pingpong.o stream.o load_hip.o)
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o reduce.o diagnose_hip.o pingpong.o stream.o load_hip.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in
@@ -98,6 +98,11 @@ $(BUILD)/gpu/%.o: csrc/%.cpp $(HEADERS) | $(BUILD)/gpu
 
 $(BUILD)/gpu/kernels.o: csrc/kernels.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# The reduce kernels' four add chains per vector stay scalar f32 adds: no
+# packed f32 instructions in this object.
+$(BUILD)/gpu/reduce.o: csrc/reduce.hip $(HEADERS) | $(BUILD)/gpu
+	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
 # csrc/diagnose.cpp (host side, in CORE) owns diagnose.o.
 $(BUILD)/gpu/diagnose_hip.o: csrc/diagnose.hip $(HEADERS) | $(BUILD)/gpu

@@ -125,6 +125,14 @@ data
                          per receive generation.  It tests what the receiver loaded, not
                          that the store landed, so the check after timing still runs.
                          Only --transport ipc --ipc-engine kernel           [P2P_VERIFY_INLINE]
+      --reduce DTYPE     u32 | f32 | bf16: receive and reduce.  A rank with receives does not
+                         store a group's messages, it adds them to its own send region (the
+                         shard of an all-reduce hop or a one-shot reduce-scatter) in one
+                         launch of the gfx950 reduce kernel: --mode ring is own + 1 incoming,
+                         allpairs own + N-1.  Payloads are finite operands of that type, the
+                         sum is checked bit for bit; flows are timed as ever (bytes pulled).
+                         --transport ipc --ipc-engine kernel, or host; sizes multiples of 4;
+                         not with --verify-inline, --diagnose, --reference or --resume
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -276,7 +284,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
                                     "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load", "--stream-sizes",
-                                    "--stream-depth", "--stream-channels", "--stream-iters"};
+                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -374,6 +382,13 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       cfg->run.verify = true;
     } else if (a == "--diagnose") {
       cfg->run.diagnose = int_arg(0);
+    } else if (a == "--reduce") {
+      const std::string v = next();
+      if (!parse_reduce_type(v, &cfg->run.reduce) || cfg->run.reduce == ReduceType::Off) {
+        std::fprintf(stderr, "p2p_matrix: --reduce '%s': the element type is u32, f32 or bf16\n", v.c_str());
+        *exit_code = 1;
+        return false;
+      }
     } else if (a == "--load") {
       const std::string v = next();
       std::string why;
@@ -510,6 +525,31 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     }
     if (!why.empty()) {
       std::fprintf(stderr, "p2p_matrix: --load cannot be combined with %s: %s\n", with.c_str(), why.c_str());
+      *exit_code = 1;
+      return false;
+    }
+  }
+  // --reduce: only where a data plane can sum (the pull engine's reduce kernel,
+  // the host transport's CPU sum), on whole 32-bit words, and not beside the
+  // options that read a receive slot as one sender's stream.
+  if (cfg->run.reduce != ReduceType::Off) {
+    std::string why;
+    if (!(cfg->transport == "host" || (cfg->transport == "ipc" && cfg->ipc_engine == "kernel")))
+      why = strfmt("needs --transport ipc --ipc-engine kernel (the gfx950 reduce kernel) or --transport host; %s%s%s sums nothing",
+                   cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",
+                   cfg->transport == "ipc" ? cfg->ipc_engine.c_str() : "");
+    for (size_t b : cfg->sizes)
+      if (why.empty() && b % 4) why = strfmt("sums 32-bit words: size %zu is not a multiple of 4", b);
+    if (why.empty() && cfg->run.inline_check)
+      why = "cannot be combined with --verify-inline: that check compares a copied message with one sender's stream";
+    if (why.empty() && cfg->run.diagnose > 0)
+      why = "cannot be combined with --diagnose: the diagnosis explains a slot by one sender's streams";
+    if (why.empty() && cfg->reference_buffers)  // set by --reference alone
+      why = "cannot be combined with --reference: that is the reference's run, which only moves its payload";
+    if (why.empty() && cfg->resume)
+      why = "cannot be combined with --resume: the runs in the file are counted by mode, direction and size alone";
+    if (!why.empty()) {
+      std::fprintf(stderr, "p2p_matrix: --reduce %s\n", why.c_str());
       *exit_code = 1;
       return false;
     }

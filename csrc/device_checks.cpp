@@ -68,6 +68,16 @@ VerifyResult DeviceChecks::verify(const void* p, size_t bytes, uint64_t seed, hi
   return verify_result();
 }
 
+VerifyResult DeviceChecks::verify_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds,
+                                          ReduceType dtype, hipStream_t stream, const StreamWait& wait) {
+  acc_.reserve(dev::kVerifyShards, [] {});
+  dev::launch_verify_reset(acc_.device(), stream);
+  dev::launch_verify_reduced(p, bytes, seeds.data(), static_cast<int>(seeds.size()), dtype, acc_.device(), stream);
+  acc_.readback(1, stream);
+  wait();
+  return verify_result();
+}
+
 std::vector<VerifyResult> DeviceChecks::verify_many(const std::vector<VerifyJob>& jobs, hipStream_t stream,
                                                     const StreamWait& wait) {
   if (jobs.empty()) return {};

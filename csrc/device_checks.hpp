@@ -76,6 +76,11 @@ class DeviceChecks {
                       unsigned max_grid, int lds_stages, bool readback);
   VerifyResult verify_result() const { return to_result(acc_.host()[0]); }
 
+  // ---- reduced buffer (Transport::verify_reduced; kernels.hpp launch_verify_reduced) ----
+  // Blocking: reset + the reduced check + finalize + readback.
+  VerifyResult verify_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, ReduceType dtype,
+                              hipStream_t stream, const StreamWait& wait);
+
   // ---- batched verify (Transport::verify_many) ----
   // One buffer at a time under --verify-impl stride or P2P_VERIFY_BATCH=0.
   std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs, hipStream_t stream, const StreamWait& wait);

@@ -72,6 +72,15 @@ class GpuTransport : public Transport {
     return checks_.diagnose(p, bytes, seed, candidates, stream_, [this] { sync(); });
   }
 
+  void fill_operand(void* p, size_t bytes, uint64_t seed, ReduceType dtype) override {
+    before_buffer_work();
+    dev::launch_fill_operand(p, bytes, seed, dtype, stream_);
+  }
+  VerifyResult verify_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, ReduceType dtype) override {
+    before_buffer_work();
+    return checks_.verify_reduced(p, bytes, seeds, dtype, stream_, [this] { sync(); });
+  }
+
   int mark() override;  // one event per mark on the main stream
   double elapsed_ms(int from, int to) override;
   void clear_marks() override { next_event_ = 0; }

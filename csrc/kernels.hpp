@@ -24,6 +24,9 @@
 //   copy    — multi-source copy for the IPC transport (remote loads over xGMI),
 //             and its checked form: the same copy comparing every word it
 //             loads with the PRNG stream due, for the inline check
+//   sum     — multi-source receive-and-reduce for the IPC transport (--reduce,
+//             reduce.hip): K loads in flight per lane, one store; with it the
+//             operand fill and the check of a reduced buffer
 //
 // Measured on MI355X (profiles/, scripts/fill_probe.hip): streaming at one
 // 16 B access per lane with one block per 4 KiB (a "full grid", up to 2^20
@@ -38,6 +41,7 @@
 #include <cstdint>
 
 #include "prng.hpp"
+#include "reduce_op.hpp"
 
 namespace p2p {
 namespace dev {
@@ -143,6 +147,62 @@ struct CheckedCopyOp : CopyOp {
 // Stream-ordered: records [0, n) become {0, ~0}.
 void launch_copy_check_reset(CopyCheck* records, int n, hipStream_t stream);
 void launch_multi_copy_checked(const CheckedCopyOp* ops, int nops, hipStream_t stream, int max_blocks = 0);
+
+// ---- multi-source receive-and-reduce (reduce.hip; --reduce) ----
+// The pull engine's other data plane: op i loads `bytes` from each of its nsrc
+// sources and stores their sum (reduce_op.hpp: element type, operand order)
+// to dst, which may be one of the sources (each lane reads a vector before it
+// writes it).  One workgroup per 4 KiB of output, one 16 B vector per lane;
+// a lane issues all nsrc 16 B loads before its first add, so nsrc links are
+// in flight at once (nsrc = 8: 32 VGPRs).  Bit i of coherent_mask: source i
+// is a hipIpc-mapped peer buffer and is read with the copy's system-scope
+// (sc0 sc1) raw-buffer loads, one range-checked descriptor per 4 KiB chunk;
+// bit kReduceDstCoherent: dst is one and is written with the coherent store.
+// Local sources and dst use non-temporal accesses.  No LDS: nothing is reused.
+// nsrc is a template parameter dispatched on the host (load burst and add
+// chain unrolled); a launch carries consecutive ops of equal nsrc, up to
+// kMaxReduceOps by value in the kernarg, so it stays graph-capturable.
+// `bytes` is a multiple of 4 (a P2P_CHECK); the 4 / 8 / 12-byte tail is done
+// word-wise by lanes 0..2 of the op's first workgroup.  Ops above 4 GiB and
+// max_blocks as in launch_multi_copy.
+constexpr int kMaxReduceSrcs = 8;
+constexpr int kMaxReduceOps = 8;
+constexpr uint32_t kReduceDstCoherent = 1u << kMaxReduceSrcs;
+struct ReduceOp {
+  void* dst = nullptr;
+  size_t bytes = 0;
+  int nsrc = 0;
+  const void* src[kMaxReduceSrcs] = {};
+  uint32_t coherent_mask = 0;
+  // bf16 only, a fan-in spread over several launches (launch_reduce_wide):
+  // partial_in: src[0] and src[1] are the f32 planes of a running sum (the low
+  // halves' sums, the high halves'), `bytes` each; partial_out: the sum is
+  // stored as those planes, unrounded, to dst and dst_hi (local memory).
+  bool partial_in = false, partial_out = false;
+  void* dst_hi = nullptr;
+};
+void launch_multi_reduce(const ReduceOp* ops, int nops, ReduceType dtype, hipStream_t stream, int max_blocks = 0);
+// A fan-in above kMaxReduceSrcs: the first launch sums operands 0..7, each
+// further one the running sum plus more, in operand order, so the bits are
+// those of one chain.  u32 and f32 carry the running sum in dst (operand 0 of
+// the next launch, up to 7 more beside it).  bf16 must not round in between:
+// its running sum travels as two f32 planes in `partial`, local scratch of
+// reduce_partial_bytes(bytes) that only such a call needs (up to 6 more
+// operands beside them), and the last launch rounds into dst.  coherent[i]
+// flags source i.
+constexpr size_t reduce_partial_bytes(size_t bytes) { return 2 * ((bytes + 15) / 16 * 16); }
+void launch_reduce_wide(void* dst, size_t bytes, const void* const* srcs, const unsigned char* coherent, int nsrcs,
+                        bool dst_coherent, ReduceType dtype, hipStream_t stream, int max_blocks = 0,
+                        void* partial = nullptr);
+// Operand stream `seed` (reduce_op.hpp operand_word over the fill's stream),
+// the fill kernel's grid; `bytes` a multiple of 4.  U32 is launch_fill.
+void launch_fill_operand(void* p, size_t bytes, uint64_t seed, ReduceType dtype, hipStream_t stream);
+// Regenerates the nseeds (<= kMaxReduceSeeds) operand streams, sums them with
+// reduce_op.hpp's function and compares with p word by word (a bf16 word
+// counts once if either half differs); the totals end in acc[0] like
+// launch_verify's (reset acc first).  Register staging: never inside timing.
+void launch_verify_reduced(const void* p, size_t bytes, const uint64_t* seeds, int nseeds, ReduceType dtype,
+                           VerifyAccum* acc, hipStream_t stream);
 
 // ---- device-initiated ping-pong (pingpong.hip) ----
 // One wave per role.  The leader writes message i (payload words = base+i+1,

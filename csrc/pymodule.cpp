@@ -112,7 +112,7 @@ class Session {
   // One (mode, dir, size) run; returns the run JSON (report.cpp schema).
   std::string run(const std::string& mode, const std::string& dir, size_t bytes, int iters, int warmup,
                   const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
-                  int diagnose, bool inline_check, const std::string& load) {
+                  int diagnose, bool inline_check, const std::string& load, const std::string& reduce) {
     LoadSpec load_spec;
     std::string why;
     P2P_CHECK(load.empty() || parse_load_spec(load, &load_spec, &why), "load '" + load + "': " + why);
@@ -129,6 +129,12 @@ class Session {
     cfg.inline_check = inline_check;
     P2P_CHECK(!inline_check || (verify && t_->supports_inline_check()),
               "inline_check needs verify=True and transport 'ipc' or 'ipc:kernel' (the pull engine's own copy kernel)");
+    // reduce="u32" | "f32" | "bf16": receive and reduce (runner.hpp RunConfig::reduce).
+    P2P_CHECK(reduce.empty() || (parse_reduce_type(reduce, &cfg.reduce) && cfg.reduce != ReduceType::Off),
+              "reduce '" + reduce + "': the element type is u32, f32 or bf16");
+    P2P_CHECK(cfg.reduce == ReduceType::Off || (t_->supports_reduce() && bytes % 4 == 0 && !inline_check && diagnose <= 0),
+              "reduce needs transport 'ipc' / 'ipc:kernel' or 'host', bytes a multiple of 4, and neither inline_check "
+              "nor diagnose");
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
@@ -372,6 +378,72 @@ py::list device_verify_many(const std::vector<std::tuple<uintptr_t, size_t, uint
   for (size_t i = 0; readback && i < dj.size(); ++i)
     out.append(py::make_tuple(bv.results()[i].mismatches, bv.results()[i].checksum, bv.results()[i].first_bad));
   return out;
+}
+
+// ---- receive-and-reduce (kernels.hpp ReduceOp) on raw pointers ----
+ReduceType reduce_type_arg(const std::string& name) {
+  ReduceType t = ReduceType::Off;
+  if (!parse_reduce_type(name, &t) || t == ReduceType::Off)
+    throw py::value_error("reduce: dtype '" + name + "' is not u32, f32 or bf16");
+  return t;
+}
+
+// dst = the sum of srcs in order; more than 8 sources go in further launches
+// with dst as their operand 0 (kernels.hpp launch_reduce_wide).
+void device_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t bytes, const std::string& dtype,
+                   uintptr_t stream, bool coherent, int max_blocks) {
+  const ReduceType t = reduce_type_arg(dtype);
+  if (srcs.empty()) throw py::value_error("reduce: at least one source");
+  std::vector<const void*> p;
+  for (uintptr_t s : srcs) p.push_back(reinterpret_cast<const void*>(s));
+  const std::vector<unsigned char> flags(srcs.size(), coherent ? 1 : 0);
+  // The f32 planes of a bf16 fan-in above 8: one scratch per process, grown
+  // behind a wait for the stream and never freed (as checks_for_current_device).
+  static void* partial = nullptr;
+  static size_t partial_bytes = 0;
+  const size_t need = t == ReduceType::Bf16 && srcs.size() > static_cast<size_t>(dev::kMaxReduceSrcs)
+                          ? dev::reduce_partial_bytes(bytes) : 0;
+  if (need > partial_bytes) {
+    stream_wait(as_stream(stream))();
+    if (partial) HIPCHECK(hipFree(partial));
+    partial = nullptr;
+    HIPCHECK(hipMalloc(&partial, need));
+    partial_bytes = need;
+  }
+  dev::launch_reduce_wide(reinterpret_cast<void*>(dst), bytes, p.data(), flags.data(), static_cast<int>(p.size()), coherent,
+                          t, as_stream(stream), max_blocks, partial);
+}
+
+// One launch_multi_reduce over [(dst, [srcs], bytes)], 1..8 sources each.
+void device_reduce_many(const std::vector<std::tuple<uintptr_t, std::vector<uintptr_t>, size_t>>& ops,
+                        const std::string& dtype, uintptr_t stream, bool coherent, int max_blocks) {
+  const ReduceType t = reduce_type_arg(dtype);
+  std::vector<dev::ReduceOp> v;
+  for (const auto& o : ops) {
+    const auto& srcs = std::get<1>(o);
+    if (srcs.empty() || srcs.size() > static_cast<size_t>(dev::kMaxReduceSrcs))
+      throw py::value_error("reduce_many: an op has 1..8 sources");
+    dev::ReduceOp r;
+    r.dst = reinterpret_cast<void*>(std::get<0>(o));
+    r.bytes = std::get<2>(o);
+    for (uintptr_t s : srcs) r.src[r.nsrc++] = reinterpret_cast<const void*>(s);
+    if (coherent) r.coherent_mask = dev::kReduceDstCoherent | ((1u << r.nsrc) - 1u);
+    v.push_back(r);
+  }
+  dev::launch_multi_reduce(v.data(), static_cast<int>(v.size()), t, as_stream(stream), max_blocks);
+}
+
+py::tuple device_verify_reduced(uintptr_t ptr, size_t bytes, const std::vector<uint64_t>& seeds, const std::string& dtype,
+                                uintptr_t stream) {
+  const ReduceType t = reduce_type_arg(dtype);
+  DeviceChecks& c = checks_for_current_device();
+  hipStream_t st = as_stream(stream);
+  VerifyResult r;
+  {
+    py::gil_scoped_release nogil;
+    r = c.verify_reduced(reinterpret_cast<const void*>(ptr), bytes, seeds, t, st, stream_wait(st));
+  }
+  return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
 
 // ---- checked copy (kernels.hpp CheckedCopyOp) on raw pointers ----
@@ -868,7 +940,7 @@ PYBIND11_MODULE(_p2pcore, m) {
       .def("run", &Session::run, py::arg("mode") = "pair", py::arg("dir") = "uni", py::arg("bytes") = 32u << 20,
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
            py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
-           py::arg("inline_check") = false, py::arg("load") = "",
+           py::arg("inline_check") = false, py::arg("load") = "", py::arg("reduce") = "",
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
@@ -1055,6 +1127,37 @@ PYBIND11_MODULE(_p2pcore, m) {
         dev::launch_multi_copy_checked(v.data(), static_cast<int>(v.size()), as_stream(stream), max_blocks);
       }, py::arg("ops"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0,
       "Stream-ordered launch of the checked copy only (timing with events): no reset, no readback.");
+  m.def("reduce", &device_reduce, py::arg("dst"), py::arg("srcs"), py::arg("bytes"), py::arg("dtype"), py::arg("stream") = 0,
+        py::arg("coherent") = false, py::arg("max_blocks") = 0,
+        "The IPC transport's gfx950 receive-and-reduce kernel: dst = srcs[0] + srcs[1] + ... in that order, element "
+        "type 'u32', 'f32' or 'bf16', bytes a multiple of 4 (coherent: every access in the cross-GPU form; more than "
+        "8 sources: further launches with dst as operand 0).");
+  m.def("reduce_many", &device_reduce_many, py::arg("ops"), py::arg("dtype"), py::arg("stream") = 0,
+        py::arg("coherent") = false, py::arg("max_blocks") = 0,
+        "The reduce kernel over several (dst, [srcs], bytes) ops, 1..8 sources each; consecutive ops of equal fan-in "
+        "share a launch.");
+  m.def("fill_operand", [](uintptr_t ptr, size_t bytes, uint64_t seed, const std::string& dtype, uintptr_t stream) {
+        dev::launch_fill_operand(reinterpret_cast<void*>(ptr), bytes, seed, reduce_type_arg(dtype), as_stream(stream));
+      }, py::arg("ptr"), py::arg("bytes"), py::arg("seed"), py::arg("dtype"), py::arg("stream") = 0,
+      "Fills with operand stream `seed` of the element type (finite floats, csrc/reduce_op.hpp).");
+  m.def("verify_reduced", &device_verify_reduced, py::arg("ptr"), py::arg("bytes"), py::arg("seeds"), py::arg("dtype"),
+        py::arg("stream") = 0,
+        "Compares the buffer with the sum of the operand streams `seeds` (operand order): (wrong 32-bit words, "
+        "checksum, first bad byte offset or 2**64-1).");
+  m.def("host_reduce", [](const std::vector<py::bytes>& operands, const std::string& dtype) {
+        const ReduceType t = reduce_type_arg(dtype);
+        if (operands.empty()) throw py::value_error("host_reduce: at least one operand");
+        std::vector<std::string> data(operands.begin(), operands.end());
+        std::vector<const void*> p;
+        for (const std::string& d : data) {
+          if (d.size() != data[0].size() || d.size() % 4) throw py::value_error("host_reduce: equal sizes, multiples of 4");
+          p.push_back(d.data());
+        }
+        std::string out(data[0].size(), '\0');
+        host_reduce(&out[0], p.data(), static_cast<int>(p.size()), out.size(), t);
+        return py::bytes(out);
+      }, py::arg("operands"), py::arg("dtype"),
+      "CPU sum of equal-sized operand byte strings in order, bit-compatible with the reduce kernel.");
   m.attr("MAX_SIGNALS") = dev::kMaxSignals;
   m.def("signal", [](const FlagList& posts, const FlagList& waits, uintptr_t status_ptr, uint64_t timeout_ticks,
                      bool release_first, uintptr_t stream, uintptr_t trap_flag) {

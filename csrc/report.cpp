@@ -265,6 +265,9 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
     std::fprintf(out, "  verification: %s (%llu mismatching words; %llu of %llu timed deliveries checked)\n",
                  bad ? "FAILED" : "OK", static_cast<unsigned long long>(bad), static_cast<unsigned long long>(checked),
                  static_cast<unsigned long long>(timed));
+  if (rec.cfg.reduce != ReduceType::Off)
+    std::fprintf(out, "  reduce: %s, every receiver sums its own shard and its incoming messages in one launch\n",
+                 reduce_type_name(rec.cfg.reduce));
   if (verified && rec.cfg.inline_check) {
     uint64_t in_flight = 0, in_bad = 0;
     for (const auto& ph : rec.phases) {
@@ -388,6 +391,15 @@ std::string run_to_json(const RunRecord& rec, int n) {
     o << ",\"load\":{\"kind\":\"" << json_escape(rec.load.kind) << "\",\"wgs\":" << rec.load.wgs
       << ",\"launch_us\":" << num(rec.load.launch_us) << ",\"alone_rate\":" << num(rec.load.alone_rate)
       << ",\"unit\":\"" << json_escape(rec.load.unit) << "\"}";
+  if (rec.cfg.reduce != ReduceType::Off) {  // present only when the option is on
+    // fan_in: the most operands any rank sums in a phase, its own shard included.
+    size_t fan_in = 0;
+    for (const auto& ph : rec.phases) {
+      std::vector<size_t> into(static_cast<size_t>(n), 0);
+      for (const auto& f : ph.flows) fan_in = std::max(fan_in, ++into[static_cast<size_t>(f.flow.dst)] + 1);
+    }
+    o << ",\"reduce\":{\"dtype\":\"" << reduce_type_name(rec.cfg.reduce) << "\",\"fan_in\":" << fan_in << "}";
+  }
   if (rec.cfg.inline_check) {  // present only when the option is on
     uint64_t in_flight = 0, in_bad = 0;
     std::vector<const PhaseResult*> phs;

@@ -136,7 +136,7 @@ std::vector<Transport::GroupFlow> group_flow_list(const Phase& phase) {
 }  // namespace
 
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen,
-                          const InlineRecords* check) {
+                          const InlineRecords* check, ReduceType reduce) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const std::vector<int> rs = remote_slots(phase, t.rank());
   const int base = gen * std::max(1, phase.max_recv_slots());
@@ -151,7 +151,9 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
     t.group_flows(bufs.send_buf(), flows, bytes);
   }
   for (size_t j = 0; j < ops.send_to.size(); ++j) t.send_to_slot(bufs.send_at(off), bytes, ops.send_to[j], base + rs[j]);
-  for (size_t i = 0; i < ops.recv_from.size(); ++i) {
+  if (reduce != ReduceType::Off && !ops.recv_from.empty())
+    t.reduce_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce);
+  for (size_t i = 0; reduce == ReduceType::Off && i < ops.recv_from.size(); ++i) {
     if (check)
       t.recv_checked(bufs.recv_buf(base + static_cast<int>(i)), bytes, ops.recv_from[i], off,
                      generation_seed(ops.recv_from[i], bytes, check->salt, gen), check->first + i);
@@ -220,7 +222,12 @@ void prepare_payload(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   P2P_CHECK(cfg.bytes <= bufs.capacity(), "message larger than buffers");
   P2P_CHECK(static_cast<int>(ops.recv_from.size()) <= bufs.slots(), "not enough receive slots");
-  if (!ops.send_to.empty())
+  // With --reduce a receiver's own send region is operand 0 of its sum.
+  if (cfg.reduce != ReduceType::Off) {
+    for (int g = 0; g < gens && !(ops.send_to.empty() && ops.recv_from.empty()); ++g)
+      t.fill_operand(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
+                     generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.reduce);
+  } else if (!ops.send_to.empty())
     for (int g = 0; g < gens; ++g)
       t.fill(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
              generation_seed(t.rank(), cfg.bytes, cfg.salt, g));
@@ -233,6 +240,24 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
                      std::vector<uint64_t>* per_slot = nullptr, std::vector<uint64_t>* per_job = nullptr) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const int per = std::max(1, phase.max_recv_slots());
+  if (cfg.reduce != ReduceType::Off) {
+    // One reduced slot per generation, against the sum of the own stream and
+    // the senders'; its findings go to the rank's first receive.
+    uint64_t bad = 0;
+    for (int g = 0; g < gens && !ops.recv_from.empty(); ++g) {
+      std::vector<uint64_t> seeds{generation_seed(t.rank(), cfg.bytes, cfg.salt, g)};
+      for (int peer : ops.recv_from) seeds.push_back(generation_seed(peer, cfg.bytes, cfg.salt, g));
+      const VerifyResult v = t.verify_reduced(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce);
+      bad += v.mismatches;
+      if (per_job)
+        for (size_t i = 0; i < ops.recv_from.size(); ++i) per_job->push_back(i ? 0 : v.mismatches);
+      if (per_slot) {
+        (*per_slot)[0] += v.mismatches;
+        if (g == 0) (*per_slot)[1] = v.checksum;
+      }
+    }
+    return bad;
+  }
   std::vector<Transport::VerifyJob> jobs;
   for (int g = 0; g < gens; ++g)
     for (size_t i = 0; i < ops.recv_from.size(); ++i)
@@ -382,7 +407,7 @@ void rechunk_until_warmup_verifies(Transport& t, Bootstrap& boot, const Phase& p
     }
     boot.barrier();
     if (active) {
-      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens);
+      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce);
       t.sync();
     }
     bad = boot.allreduce_sum_u64(local_mismatches());
@@ -553,6 +578,11 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
     return res;
   }
   P2P_CHECK(cfg.iters >= 1, "iters must be >= 1");
+  if (cfg.reduce != ReduceType::Off) {
+    P2P_CHECK(t.supports_reduce(), "reduce: this transport cannot sum a group's messages (ipc with the kernel engine, or host)");
+    P2P_CHECK(cfg.bytes % 4 == 0, "reduce: the message size must be a multiple of 4");
+    P2P_CHECK(!cfg.inline_check && cfg.diagnose == 0, "reduce: not with the inline check or the diagnosis");
+  }
   // Relay ranks of a multi-path transport post (and time) the phase too; a
   // flow is still charged by its two endpoints only.
   const bool active = posts_phase(t, phase, me);
@@ -574,7 +604,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   const double hooked0 = now_seconds();
   if (cfg.before_timing) cfg.before_timing();
   if (active) {
-    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens);
+    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce);
     t.sync();
   }
   if (cfg.verify && cfg.warmup > 0) {
@@ -618,7 +648,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   auto post = [&](int i) {
     if (skip_some) t.set_discard(i % 2 == 0);
     const InlineRecords rec{static_cast<size_t>(i) * nrecv, cfg.salt};
-    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr);
+    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce);
   };
 
   double my_seconds = 0;

@@ -69,6 +69,15 @@ struct RunConfig {
   // the check of the slots after timing runs as always.  Warm-up iterations
   // are posted unchecked.  Off: nothing changes.
   bool inline_check = false;
+  // Receive-and-reduce (--reduce; transport.hpp reduce_from): send regions
+  // hold operand streams of this element type, and a rank with receives posts
+  // one reduce_from per iteration instead of its receives: its own send
+  // region plus every incoming message, summed into receive slot 0 of the
+  // iteration's generation.  Flows are timed and reported as ever (bytes
+  // pulled per flow); the check after timing compares each kept generation's
+  // slot 0 with the regenerated sum and charges it to the rank's first flow.
+  // Off: nothing changes.
+  ReduceType reduce = ReduceType::Off;
   // Hooks around what a phase measures (--load brackets it with a background
   // load): run_phase calls them on every rank of a non-idle phase, in both
   // timings.  before_timing: after the payload and the poison are posted,
@@ -218,8 +227,10 @@ struct InlineRecords {
   size_t first = 0;
   uint64_t salt = 0;
 };
+// With `reduce`, the receives are posted as one Transport::reduce_from into
+// slot gen * phase.max_recv_slots(), the local operand being send region gen.
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0,
-                          const InlineRecords* check = nullptr);
+                          const InlineRecords* check = nullptr, ReduceType reduce = ReduceType::Off);
 
 // Receive generations for verified runs of messages up to `max_bytes` with
 // `slots` receive slots per iteration and up to `iters` iterations: as many as

@@ -27,6 +27,7 @@
 #include "background_load.hpp"
 #include "diagnose.hpp"
 #include "prng.hpp"
+#include "reduce_op.hpp"
 
 namespace p2p {
 
@@ -111,6 +112,27 @@ class Transport {
     recv_from(p, bytes, peer, src_offset);
   }
   virtual std::vector<InlineCheck> inline_check_results() { return {}; }
+
+  // ---- receive-and-reduce (--reduce; reduce_op.hpp) ----
+  // The receiver does not store a group's incoming messages, it adds them to
+  // its own shard: dst = local_src + the message of every peer in `peers`, in
+  // that order, each read at `src_offset` of the peer's registered send buffer
+  // like recv_from.  Posted inside a group, once per group at most; dst is a
+  // registered receive slot, `bytes` a multiple of 4.  The IPC pull engine
+  // does it in one launch of the gfx950 reduce kernel, the host transport
+  // receives into scratch and sums on the CPU.  A discarding transport runs
+  // its protocol and leaves dst alone.
+  //   fill_operand    fill() with the operand map of `dtype` applied;
+  //   verify_reduced  blocking: p against the sum of the operand streams
+  //                   `seeds` (operand order), a wrong word counted once.
+  virtual bool supports_reduce() const { return false; }
+  virtual void fill_operand(void* /*p*/, size_t /*bytes*/, uint64_t /*seed*/, ReduceType /*dtype*/) {}
+  virtual void reduce_from(void* /*dst*/, size_t /*bytes*/, const void* /*local_src*/, const std::vector<int>& /*peers*/,
+                           size_t /*src_offset*/, ReduceType /*dtype*/) {}
+  virtual VerifyResult verify_reduced(const void* /*p*/, size_t /*bytes*/, const std::vector<uint64_t>& /*seeds*/,
+                                      ReduceType /*dtype*/) {
+    return {};
+  }
 
   // Multi-path transports (IPC relay engine) move parts of a message through
   // ranks that are neither its sender nor its receiver, so every rank must

@@ -66,6 +66,41 @@ VerifyResult host_verify(const void* p, size_t bytes, uint64_t seed) {
   return r;
 }
 
+void host_reduce(void* out, const void* const* operands, int k, size_t bytes, ReduceType t) {
+  P2P_CHECK(k >= 1 && bytes % 4 == 0, "host_reduce: at least one operand, bytes a multiple of 4");
+  std::vector<uint32_t> w(static_cast<size_t>(k));
+  for (size_t i = 0; i < bytes; i += 4) {
+    for (int j = 0; j < k; ++j) std::memcpy(&w[static_cast<size_t>(j)], static_cast<const char*>(operands[j]) + i, 4);
+    const uint32_t r = reduce_word(w.data(), k, t);
+    std::memcpy(static_cast<char*>(out) + i, &r, 4);
+  }
+}
+
+void host_fill_operand(void* p, size_t bytes, uint64_t seed, ReduceType t) {
+  P2P_CHECK(bytes % 4 == 0, "host_fill_operand: bytes must be a multiple of 4");
+  for (size_t i = 0; i < bytes / 4; ++i) {
+    const uint32_t w = operand_word(prng_word(seed, i), t);
+    std::memcpy(static_cast<char*>(p) + 4 * i, &w, 4);
+  }
+}
+
+VerifyResult host_verify_reduced(const void* p, size_t bytes, const uint64_t* seeds, int nseeds, ReduceType t) {
+  P2P_CHECK(nseeds >= 1 && bytes % 4 == 0, "host_verify_reduced: at least one seed, bytes a multiple of 4");
+  VerifyResult r;
+  std::vector<uint32_t> w(static_cast<size_t>(nseeds));
+  for (size_t i = 0; i < bytes / 4; ++i) {
+    for (int j = 0; j < nseeds; ++j) w[static_cast<size_t>(j)] = operand_word(prng_word(seeds[j], i), t);
+    uint32_t got;
+    std::memcpy(&got, static_cast<const char*>(p) + 4 * i, 4);
+    r.checksum += got;
+    if (got != reduce_word(w.data(), nseeds, t)) {
+      if (!r.mismatches) r.first_bad = 4 * i;
+      ++r.mismatches;
+    }
+  }
+  return r;
+}
+
 namespace {
 
 void sockopts(int fd) {
@@ -164,10 +199,31 @@ class HostTransport final : public Transport {
     return host_diagnose_extents(p, bytes, seed, candidates);
   }
 
+  // ---- receive-and-reduce: each message into scratch, then the CPU sum ----
+  bool supports_reduce() const override { return true; }
+  void fill_operand(void* p, size_t bytes, uint64_t seed, ReduceType dtype) override {
+    host_fill_operand(p, bytes, seed, dtype);
+  }
+  VerifyResult verify_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, ReduceType dtype) override {
+    return host_verify_reduced(p, bytes, seeds.data(), static_cast<int>(seeds.size()), dtype);
+  }
+  void reduce_from(void* dst, size_t bytes, const void* local_src, const std::vector<int>& peers, size_t,
+                   ReduceType dtype) override {
+    P2P_CHECK(in_group_ && !reduce_.dst, "host transport: one reduce_from per group, inside the group");
+    P2P_CHECK(bytes % 4 == 0, "host transport: a reduced message is a multiple of 4 bytes");
+    reduce_ = {dst, bytes, local_src, dtype, peers.size()};
+    if (scratch_.size() < bytes * peers.size()) scratch_.resize(bytes * peers.size());
+    for (size_t i = 0; i < peers.size(); ++i) {
+      P2P_CHECK(peers[i] >= 0 && peers[i] < n_, "bad peer");
+      ops_.push_back({false, peers[i], scratch_.data() + i * bytes, bytes});
+    }
+  }
+
   void group_begin() override {
     P2P_CHECK(!in_group_, "nested group");
     in_group_ = true;
     ops_.clear();
+    reduce_ = {};
   }
   void send(const void* p, size_t bytes, int peer) override {
     P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
@@ -188,6 +244,13 @@ class HostTransport final : public Transport {
       if (op.is_send) sent[static_cast<size_t>(op.peer)] += op.bytes;
     emulate_link_delay(sent, rank_);
     run_ops();
+    // Injected skip fault: the messages were read off the wire, the sum is not made.
+    if (reduce_.dst && !discarding()) {
+      std::vector<const void*> operands{reduce_.local_src};
+      for (size_t i = 0; i < reduce_.npeers; ++i) operands.push_back(scratch_.data() + i * reduce_.bytes);
+      host_reduce(reduce_.dst, operands.data(), static_cast<int>(operands.size()), reduce_.bytes, reduce_.dtype);
+    }
+    reduce_ = {};
   }
 
   int mark() override {
@@ -199,6 +262,13 @@ class HostTransport final : public Transport {
   void sync() override {}
 
  private:
+  struct PendingReduce {
+    void* dst = nullptr;
+    size_t bytes = 0;
+    const void* local_src = nullptr;
+    ReduceType dtype = ReduceType::Off;
+    size_t npeers = 0;
+  };
   struct Op {
     bool is_send;
     int peer;
@@ -301,6 +371,8 @@ class HostTransport final : public Transport {
   std::vector<int> fds_;
   bool in_group_ = false;
   std::vector<Op> ops_;
+  PendingReduce reduce_;       // the open group's reduce_from, summed in group_end()
+  std::vector<char> scratch_;  // its incoming messages, one after the other
   std::vector<double> marks_;
 };
 

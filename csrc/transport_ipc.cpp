@@ -121,6 +121,7 @@ class IpcTransport final : public GpuTransport {
                    relayed_stripes_);
     for (auto& r : regs_) close_registration(r);
     regs_.clear();
+    if (partial_) (void)hipFree(partial_);
     ping_.release();
     dstream_.release();
     release_sync_pages();
@@ -193,6 +194,7 @@ class IpcTransport final : public GpuTransport {
     in_group_ = true;
     ops_.clear();
     checked_ops_.clear();
+    reduce_ = {};
     if (plan_) plan_->group_begin();
   }
 
@@ -258,6 +260,32 @@ class IpcTransport final : public GpuTransport {
   }
   std::vector<InlineCheck> inline_check_results() override {
     return checks_.records_read(stream_, [this] { sync(); });
+  }
+
+  // ---- receive-and-reduce (transport.hpp): the pull engine's reduce kernel
+  // loads the own shard and every peer's message and stores their sum, one
+  // launch per group (kernels.hpp launch_reduce_wide).
+  bool supports_reduce() const override { return engine_ == "kernel"; }
+  void reduce_from(void* dst, size_t bytes, const void* local_src, const std::vector<int>& peers, size_t src_offset,
+                   ReduceType dtype) override {
+    P2P_CHECK(supports_reduce(), "ipc transport: --reduce needs --ipc-engine kernel");
+    P2P_CHECK(in_group_ && !reduce_.dst, "ipc transport: one reduce_from per group, inside the group");
+    const Registration* reg = nullptr;
+    for (const auto& r : regs_)
+      if (slot_of(r, dst) >= 0 && bytes <= r.slot_bytes) reg = &r;
+    P2P_CHECK(reg, "ipc transport reduces only into a registered receive slot");
+    P2P_CHECK(src_offset + bytes <= reg->send_bytes, "ipc transport: reduce beyond the peer's send buffer");
+    if (discarding()) return;  // injected skip fault: the launch is not issued
+    reduce_.dst = dst;
+    reduce_.bytes = bytes;
+    reduce_.dtype = dtype;
+    reduce_.srcs.assign(1, local_src);
+    reduce_.coherent.assign(1, 0);
+    for (int peer : peers) {
+      P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
+      reduce_.srcs.push_back(static_cast<const char*>(reg->peer_send.ptr[static_cast<size_t>(peer)]) + src_offset);
+      reduce_.coherent.push_back(peer != rank_);
+    }
   }
 
   void group_end() override {
@@ -398,6 +426,22 @@ class IpcTransport final : public GpuTransport {
     // Kernel engine: the checked kernel when the group has checked receives
     // (the runner posts a group either all checked or all plain; plain ones
     // next to them go in the plain kernel), the plain kernel otherwise.
+    if (reduce_.dst) {
+      // A bf16 fan-in above 8 (more than 8 ranks) carries f32 partial sums in scratch.
+      const size_t need = reduce_.dtype == ReduceType::Bf16 && reduce_.srcs.size() > static_cast<size_t>(dev::kMaxReduceSrcs)
+                              ? dev::reduce_partial_bytes(reduce_.bytes) : 0;
+      if (need > partial_bytes_) {
+        P2P_CHECK(!capturing_, "ipc transport: the first wide bf16 reduce of a size cannot be inside a graph capture");
+        sync();  // the old scratch may still be in use
+        if (partial_) HIPCHECK(hipFree(partial_));
+        partial_ = nullptr;
+        HIPCHECK(hipMalloc(&partial_, need));
+        partial_bytes_ = need;
+      }
+      dev::launch_reduce_wide(reduce_.dst, reduce_.bytes, reduce_.srcs.data(), reduce_.coherent.data(),
+                              static_cast<int>(reduce_.srcs.size()), false, reduce_.dtype, stream_, 0, partial_);
+      reduce_ = {};
+    }
     if (!checked_ops_.empty()) {
       dev::launch_multi_copy_checked(checked_ops_.data(), static_cast<int>(checked_ops_.size()), stream_);
       checked_ops_.clear();
@@ -555,6 +599,16 @@ class IpcTransport final : public GpuTransport {
 
   // Pull kernel: receives checked as they are copied.
   std::vector<dev::CheckedCopyOp> checked_ops_;
+  // Pull kernel: the open group's reduce_from, launched in flush().
+  struct PendingReduce {
+    void* dst = nullptr;
+    size_t bytes = 0;
+    ReduceType dtype = ReduceType::Off;
+    std::vector<const void*> srcs;   // operand 0: the own shard
+    std::vector<unsigned char> coherent;  // per source: a peer's mapped buffer
+  } reduce_;
+  void* partial_ = nullptr;  // f32 planes of a wide bf16 sum (kernels.hpp reduce_partial_bytes)
+  size_t partial_bytes_ = 0;
 
   // SDMA: the fork / join pool.
   std::vector<hipStream_t> side_;

@@ -12,9 +12,13 @@ from .buffers import (  # noqa: F401
     diagnose_records,
     fill_,
     reference_bytes,
+    reduce_,
     reference_copy_check,
     reference_diagnose,
+    reference_operands,
+    reference_reduce,
     reference_verify,
     reference_words,
     verify,
+    words_to_bytes,
 )

@@ -193,6 +193,78 @@ def reference_copy_check(src: torch.Tensor, seed: int, stream_offset: int = 0) -
     return CopyCheck(int(bad.numel()), first)
 
 
+# ------------------------------------------------------- receive-and-reduce --
+
+REDUCE_DTYPES = ("u32", "f32", "bf16")
+
+
+def reduce_(dst: torch.Tensor, srcs, dtype: str, *, coherent: bool = False, max_blocks: int = 0,
+            stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """``dst`` = ``srcs[0] + srcs[1] + ...`` in that order with the gfx950
+    reduce kernel (stream-ordered): the tensors' bytes are read as elements of
+    ``dtype`` ('u32', 'f32' or 'bf16'; csrc/reduce_op.hpp).  More than 8
+    sources take further launches with ``dst`` as their operand 0."""
+    nbytes = _check_tensor(dst)
+    if any(_check_tensor(s) != nbytes for s in srcs):
+        raise ValueError("reduce_: dst and every source have one size")
+    require_native().reduce(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, dtype, _stream(stream), coherent,
+                            max_blocks)
+    return dst
+
+
+def reference_operands(nbytes: int, seed: int, dtype: str, device="cpu") -> torch.Tensor:
+    """The first ``nbytes`` (a multiple of 4) of operand stream ``seed`` as
+    int64 words in [0, 2**32): :func:`reference_words` through the operand map
+    of ``dtype``, which pins every float's exponent field into [64, 127]."""
+    assert nbytes % 4 == 0 and dtype in REDUCE_DTYPES
+    w = reference_words(0, nbytes // 4, seed, device)
+    if dtype == "f32":
+        w = (w & 0xBFFFFFFF) | 0x20000000
+    elif dtype == "bf16":
+        w = (w & 0xBFFFBFFF) | 0x20002000
+    return w
+
+
+def _words_to_f32(w: torch.Tensor) -> torch.Tensor:
+    return torch.where(w >= 2**31, w - 2**32, w).to(torch.int32).view(torch.float32)
+
+
+def _f32_to_words(f: torch.Tensor) -> torch.Tensor:
+    return f.contiguous().view(torch.int32).to(torch.int64) & M32
+
+
+def reference_reduce(operands, dtype: str) -> torch.Tensor:
+    """The sum of ``operands`` (int64 word tensors as :func:`reference_operands`
+    gives them) in order, as int64 words: u32 wraps mod 2**32; f32 is a chain
+    of ``torch.float32`` adds on the CPU; bf16 widens both halves of a word to
+    float32, chains the adds and rounds once with ``.to(torch.bfloat16)``."""
+    assert dtype in REDUCE_DTYPES and len(operands) >= 1
+    ops = [o.cpu() for o in operands]
+    if dtype == "u32":
+        acc = ops[0].clone()
+        for o in ops[1:]:
+            acc = (acc + o) & M32
+        return acc
+    if dtype == "f32":
+        acc = _words_to_f32(ops[0]).clone()
+        for o in ops[1:]:
+            acc = acc + _words_to_f32(o)
+        return _f32_to_words(acc)
+    lo = _words_to_f32((ops[0] << 16) & M32).clone()
+    hi = _words_to_f32(ops[0] & 0xFFFF0000).clone()
+    for o in ops[1:]:
+        lo = lo + _words_to_f32((o << 16) & M32)
+        hi = hi + _words_to_f32(o & 0xFFFF0000)
+    lo16 = lo.to(torch.bfloat16).view(torch.int16).to(torch.int64) & 0xFFFF
+    hi16 = hi.to(torch.bfloat16).view(torch.int16).to(torch.int64) & 0xFFFF
+    return lo16 | (hi16 << 16)
+
+
+def words_to_bytes(w: torch.Tensor) -> torch.Tensor:
+    """int64 words in [0, 2**32) as a uint8 tensor (little-endian)."""
+    return torch.stack([(w >> (8 * k)) & 0xFF for k in range(4)], dim=1).to(torch.uint8).reshape(-1)
+
+
 # ---------------------------------------------------------------- diagnosis --
 
 class GranuleRecord(NamedTuple):
