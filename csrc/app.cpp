@@ -133,6 +133,14 @@ data
                          sum is checked bit for bit; flows are timed as ever (bytes pulled).
                          --transport ipc --ipc-engine kernel, or host; sizes multiples of 4;
                          not with --verify-inline, --diagnose, --reference or --resume
+      --wire FORMAT      mxfp8 | mxfp4: block-scaled payloads.  Payloads are bf16; the link
+                         carries their OCP microscaling image (8- or 4-bit elements, one
+                         power-of-two scale byte per 32 elements: 0.516 or 0.266 of the
+                         payload) and the receiver widens it back to bf16 as it pulls, in
+                         the gfx950 unpack kernel.  Flows are timed and reported in payload
+                         bytes (the bf16 delivered); every kept slot is checked bit for bit.
+                         --transport ipc --ipc-engine kernel, or host; sizes multiples of 64;
+                         not with --reduce, --verify-inline, --diagnose, --reference or --resume
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -284,7 +292,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
                                     "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load", "--stream-sizes",
-                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce"};
+                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -386,6 +394,13 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       const std::string v = next();
       if (!parse_reduce_type(v, &cfg->run.reduce) || cfg->run.reduce == ReduceType::Off) {
         std::fprintf(stderr, "p2p_matrix: --reduce '%s': the element type is u32, f32 or bf16\n", v.c_str());
+        *exit_code = 1;
+        return false;
+      }
+    } else if (a == "--wire") {
+      const std::string v = next();
+      if (!parse_wire_format(v, &cfg->run.wire) || cfg->run.wire == WireFormat::Off) {
+        std::fprintf(stderr, "p2p_matrix: --wire '%s': the format is mxfp8 or mxfp4\n", v.c_str());
         *exit_code = 1;
         return false;
       }
@@ -550,6 +565,33 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       why = "cannot be combined with --resume: the runs in the file are counted by mode, direction and size alone";
     if (!why.empty()) {
       std::fprintf(stderr, "p2p_matrix: --reduce %s\n", why.c_str());
+      *exit_code = 1;
+      return false;
+    }
+  }
+  // --wire: only where a data plane can widen (the pull engine's unpack
+  // kernel, the host transport's CPU unpack), on whole blocks of 32 bf16, and
+  // not beside the options that read a slot or a send region as a raw stream.
+  if (cfg->run.wire != WireFormat::Off) {
+    std::string why;
+    if (!(cfg->transport == "host" || (cfg->transport == "ipc" && cfg->ipc_engine == "kernel")))
+      why = strfmt("needs --transport ipc --ipc-engine kernel (the gfx950 unpack kernel) or --transport host; %s%s%s widens nothing",
+                   cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",
+                   cfg->transport == "ipc" ? cfg->ipc_engine.c_str() : "");
+    for (size_t b : cfg->sizes)
+      if (why.empty() && b % kWireBlockBytes) why = strfmt("scales blocks of 32 bf16: size %zu is not a multiple of 64", b);
+    if (why.empty() && cfg->run.reduce != ReduceType::Off)
+      why = "cannot be combined with --reduce: the reduce kernel sums unpacked operands";
+    if (why.empty() && cfg->run.inline_check)
+      why = "cannot be combined with --verify-inline: that check compares a copied message with the raw stream";
+    if (why.empty() && cfg->run.diagnose > 0)
+      why = "cannot be combined with --diagnose: the diagnosis explains a slot by raw streams";
+    if (why.empty() && cfg->reference_buffers)  // set by --reference alone
+      why = "cannot be combined with --reference: that is the reference's run, which only moves its payload";
+    if (why.empty() && cfg->resume)
+      why = "cannot be combined with --resume: the runs in the file are counted by mode, direction and size alone";
+    if (!why.empty()) {
+      std::fprintf(stderr, "p2p_matrix: --wire %s\n", why.c_str());
       *exit_code = 1;
       return false;
     }

@@ -78,6 +78,16 @@ VerifyResult DeviceChecks::verify_reduced(const void* p, size_t bytes, const std
   return verify_result();
 }
 
+VerifyResult DeviceChecks::verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt,
+                                           hipStream_t stream, const StreamWait& wait) {
+  acc_.reserve(dev::kVerifyShards, [] {});
+  dev::launch_verify_reset(acc_.device(), stream);
+  dev::launch_verify_unpacked(p, payload_bytes, seed, fmt, acc_.device(), stream);
+  acc_.readback(1, stream);
+  wait();
+  return verify_result();
+}
+
 std::vector<VerifyResult> DeviceChecks::verify_many(const std::vector<VerifyJob>& jobs, hipStream_t stream,
                                                     const StreamWait& wait) {
   if (jobs.empty()) return {};

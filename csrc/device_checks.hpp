@@ -81,6 +81,11 @@ class DeviceChecks {
   VerifyResult verify_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, ReduceType dtype,
                               hipStream_t stream, const StreamWait& wait);
 
+  // ---- unpacked buffer (Transport::verify_unpacked; kernels.hpp launch_verify_unpacked) ----
+  // Blocking: reset + the unpacked check + finalize + readback.
+  VerifyResult verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt, hipStream_t stream,
+                               const StreamWait& wait);
+
   // ---- batched verify (Transport::verify_many) ----
   // One buffer at a time under --verify-impl stride or P2P_VERIFY_BATCH=0.
   std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs, hipStream_t stream, const StreamWait& wait);

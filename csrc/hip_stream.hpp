@@ -81,6 +81,15 @@ class GpuTransport : public Transport {
     return checks_.verify_reduced(p, bytes, seeds, dtype, stream_, [this] { sync(); });
   }
 
+  void fill_packed(void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt) override {
+    before_buffer_work();
+    dev::launch_fill_packed(p, payload_bytes, seed, fmt, stream_);
+  }
+  VerifyResult verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt) override {
+    before_buffer_work();
+    return checks_.verify_unpacked(p, payload_bytes, seed, fmt, stream_, [this] { sync(); });
+  }
+
   int mark() override;  // one event per mark on the main stream
   double elapsed_ms(int from, int to) override;
   void clear_marks() override { next_event_ = 0; }

@@ -27,6 +27,9 @@
 //   sum     — multi-source receive-and-reduce for the IPC transport (--reduce,
 //             reduce.hip): K loads in flight per lane, one store; with it the
 //             operand fill and the check of a reduced buffer
+//   wire    — block-scaled payloads for the IPC transport (--wire, wire.hip):
+//             the receive that widens MXFP8 / MXFP4 to bf16 as it pulls, the
+//             sender's pack, and the check of an unpacked buffer
 //
 // Measured on MI355X (profiles/, scripts/fill_probe.hip): streaming at one
 // 16 B access per lane with one block per 4 KiB (a "full grid", up to 2^20
@@ -42,6 +45,7 @@
 
 #include "prng.hpp"
 #include "reduce_op.hpp"
+#include "wire_op.hpp"
 
 namespace p2p {
 namespace dev {
@@ -203,6 +207,46 @@ void launch_fill_operand(void* p, size_t bytes, uint64_t seed, ReduceType dtype,
 // launch_verify's (reset acc first).  Register staging: never inside timing.
 void launch_verify_reduced(const void* p, size_t bytes, const uint64_t* seeds, int nseeds, ReduceType dtype,
                            VerifyAccum* acc, hipStream_t stream);
+
+// ---- block-scaled wire formats (wire.hip; --wire) ----
+// The pull engine's third data plane: op i reads the MXFP8 / MXFP4 wire image
+// (wire_op.hpp: wire_bytes(payload_bytes)) at src and stores payload_bytes of
+// bf16 to dst.  A 256-thread workgroup takes whole tiles (128 blocks, 8 KiB
+// of payload), 16 elements per lane: 16 B / 8 B element loads and one scale
+// byte load per unit, v_cvt_scalef32_pk_bf16_fp8 / _fp4, two 16 B stores.
+// coherent: src is a hipIpc-mapped peer buffer and is read with system-scope
+// (sc0 sc1) raw-buffer loads through one range-checked descriptor per tile;
+// dst_coherent: dst is one and is written the same way.  Local memory uses
+// non-temporal accesses.  Up to kMaxUnpackOps ops per launch by value in the
+// kernarg (more: further launches), workgroups split over them by tiles
+// (split_blocks); max_blocks > 0 caps the grid and the kernel strides.
+// payload_bytes is a multiple of 64 (a P2P_CHECK).  `lanes` picks the lane
+// mapping: Split (a lane's two units lie 4 KiB of payload apart, both stores
+// coalesced), Contiguous (one wider load, stores with a 32 B lane stride);
+// Auto is the one measured faster.
+constexpr int kMaxUnpackOps = 32;
+enum class WireLanes : int { Auto = 0, Contiguous = 1, Split = 2 };
+struct UnpackOp {
+  void* dst = nullptr;
+  const void* src = nullptr;
+  size_t payload_bytes = 0;
+  bool coherent = false;
+  bool dst_coherent = false;
+};
+void launch_multi_unpack(const UnpackOp* ops, int nops, WireFormat fmt, hipStream_t stream, int max_blocks = 0,
+                         WireLanes lanes = WireLanes::Auto);
+// The sender's quantise step: payload_bytes of bf16 -> the wire image.  A lane
+// loads the 2 (mxfp8) or 4 (mxfp4) vectors that yield one 16 B element store;
+// the scale bytes of a tile leave through LDS as 16 B stores.
+void launch_pack(void* wire, const void* payload, size_t payload_bytes, WireFormat fmt, hipStream_t stream);
+// The same kernel fed by wire_operand_word over the fill's stream `seed`: a
+// send region gets the wire image of its operand stream, no bf16 staging.
+void launch_fill_packed(void* wire, size_t payload_bytes, uint64_t seed, WireFormat fmt, hipStream_t stream);
+// Regenerates operand stream `seed`, applies wire_op.hpp's pack and unpack
+// per block (4 lanes each) and compares with p word by word; the totals end
+// in acc[0] like launch_verify's (reset acc first).  Never inside timing.
+void launch_verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt, VerifyAccum* acc,
+                            hipStream_t stream);
 
 // ---- device-initiated ping-pong (pingpong.hip) ----
 // One wave per role.  The leader writes message i (payload words = base+i+1,

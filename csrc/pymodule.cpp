@@ -112,7 +112,8 @@ class Session {
   // One (mode, dir, size) run; returns the run JSON (report.cpp schema).
   std::string run(const std::string& mode, const std::string& dir, size_t bytes, int iters, int warmup,
                   const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
-                  int diagnose, bool inline_check, const std::string& load, const std::string& reduce) {
+                  int diagnose, bool inline_check, const std::string& load, const std::string& reduce,
+                  const std::string& wire) {
     LoadSpec load_spec;
     std::string why;
     P2P_CHECK(load.empty() || parse_load_spec(load, &load_spec, &why), "load '" + load + "': " + why);
@@ -135,6 +136,13 @@ class Session {
     P2P_CHECK(cfg.reduce == ReduceType::Off || (t_->supports_reduce() && bytes % 4 == 0 && !inline_check && diagnose <= 0),
               "reduce needs transport 'ipc' / 'ipc:kernel' or 'host', bytes a multiple of 4, and neither inline_check "
               "nor diagnose");
+    // wire="mxfp8" | "mxfp4": block-scaled payloads (runner.hpp RunConfig::wire).
+    P2P_CHECK(wire.empty() || (parse_wire_format(wire, &cfg.wire) && cfg.wire != WireFormat::Off),
+              "wire '" + wire + "': the format is mxfp8 or mxfp4");
+    P2P_CHECK(cfg.wire == WireFormat::Off || (t_->supports_wire() && bytes % kWireBlockBytes == 0 && reduce.empty() &&
+                                              !inline_check && diagnose <= 0),
+              "wire needs transport 'ipc' / 'ipc:kernel' or 'host', bytes a multiple of 64, and none of reduce, "
+              "inline_check and diagnose");
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
@@ -442,6 +450,52 @@ py::tuple device_verify_reduced(uintptr_t ptr, size_t bytes, const std::vector<u
   {
     py::gil_scoped_release nogil;
     r = c.verify_reduced(reinterpret_cast<const void*>(ptr), bytes, seeds, t, st, stream_wait(st));
+  }
+  return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
+}
+
+// ---- block-scaled wire formats (kernels.hpp UnpackOp, wire_op.hpp) on raw pointers ----
+WireFormat wire_format_arg(const std::string& name) {
+  WireFormat f = WireFormat::Off;
+  if (!parse_wire_format(name, &f) || f == WireFormat::Off) throw py::value_error("wire: format '" + name + "' is not mxfp8 or mxfp4");
+  return f;
+}
+size_t wire_payload_arg(size_t payload_bytes) {
+  if (payload_bytes % kWireBlockBytes) throw py::value_error("wire: the payload is a multiple of 64 bytes (blocks of 32 bf16)");
+  return payload_bytes;
+}
+dev::WireLanes wire_lanes_arg(const std::string& name) {
+  if (name == "auto") return dev::WireLanes::Auto;
+  if (name == "contiguous") return dev::WireLanes::Contiguous;
+  if (name == "split") return dev::WireLanes::Split;
+  throw py::value_error("wire: lanes '" + name + "' is not auto, contiguous or split");
+}
+
+// One launch_multi_unpack over [(dst, src, payload_bytes)].
+void device_wire_unpack_many(const std::vector<std::tuple<uintptr_t, uintptr_t, size_t>>& ops, const std::string& fmt,
+                             uintptr_t stream, bool coherent, int max_blocks, const std::string& lanes) {
+  const WireFormat f = wire_format_arg(fmt);
+  std::vector<dev::UnpackOp> v;
+  for (const auto& o : ops) {
+    dev::UnpackOp u;
+    u.dst = reinterpret_cast<void*>(std::get<0>(o));
+    u.src = reinterpret_cast<const void*>(std::get<1>(o));
+    u.payload_bytes = wire_payload_arg(std::get<2>(o));
+    u.coherent = u.dst_coherent = coherent;
+    v.push_back(u);
+  }
+  dev::launch_multi_unpack(v.data(), static_cast<int>(v.size()), f, as_stream(stream), max_blocks, wire_lanes_arg(lanes));
+}
+
+py::tuple device_verify_unpacked(uintptr_t ptr, size_t payload_bytes, uint64_t seed, const std::string& fmt, uintptr_t stream) {
+  const WireFormat f = wire_format_arg(fmt);
+  wire_payload_arg(payload_bytes);
+  DeviceChecks& c = checks_for_current_device();
+  hipStream_t st = as_stream(stream);
+  VerifyResult r;
+  {
+    py::gil_scoped_release nogil;
+    r = c.verify_unpacked(reinterpret_cast<const void*>(ptr), payload_bytes, seed, f, st, stream_wait(st));
   }
   return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
@@ -940,7 +994,7 @@ PYBIND11_MODULE(_p2pcore, m) {
       .def("run", &Session::run, py::arg("mode") = "pair", py::arg("dir") = "uni", py::arg("bytes") = 32u << 20,
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
            py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
-           py::arg("inline_check") = false, py::arg("load") = "", py::arg("reduce") = "",
+           py::arg("inline_check") = false, py::arg("load") = "", py::arg("reduce") = "", py::arg("wire") = "",
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
@@ -1158,6 +1212,48 @@ PYBIND11_MODULE(_p2pcore, m) {
         return py::bytes(out);
       }, py::arg("operands"), py::arg("dtype"),
       "CPU sum of equal-sized operand byte strings in order, bit-compatible with the reduce kernel.");
+  m.def("wire_bytes", [](size_t payload_bytes, const std::string& fmt) {
+        return wire_bytes(wire_payload_arg(payload_bytes), wire_format_arg(fmt));
+      }, py::arg("payload_bytes"), py::arg("fmt"), "Size of the wire image of payload_bytes of bf16 (csrc/wire_op.hpp).");
+  m.def("wire_pack", [](uintptr_t dst, uintptr_t src, size_t payload_bytes, const std::string& fmt, uintptr_t stream) {
+        dev::launch_pack(reinterpret_cast<void*>(dst), reinterpret_cast<const void*>(src), wire_payload_arg(payload_bytes),
+                         wire_format_arg(fmt), as_stream(stream));
+      }, py::arg("dst"), py::arg("src"), py::arg("payload_bytes"), py::arg("fmt"), py::arg("stream") = 0,
+      "The gfx950 pack kernel: payload_bytes of bf16 at src -> wire_bytes() of 'mxfp8' or 'mxfp4' at dst.");
+  m.def("wire_unpack", [](uintptr_t dst, uintptr_t src, size_t payload_bytes, const std::string& fmt, uintptr_t stream,
+                          bool coherent, int max_blocks, const std::string& lanes) {
+        device_wire_unpack_many({{dst, src, payload_bytes}}, fmt, stream, coherent, max_blocks, lanes);
+      }, py::arg("dst"), py::arg("src"), py::arg("payload_bytes"), py::arg("fmt"), py::arg("stream") = 0,
+      py::arg("coherent") = false, py::arg("max_blocks") = 0, py::arg("lanes") = "auto",
+      "The IPC transport's gfx950 unpack kernel: the wire image at src -> payload_bytes of bf16 at dst (coherent: every "
+      "access in the cross-GPU form; lanes: 'auto', 'contiguous' or 'split' lane mapping).");
+  m.def("wire_unpack_many", &device_wire_unpack_many, py::arg("ops"), py::arg("fmt"), py::arg("stream") = 0,
+        py::arg("coherent") = false, py::arg("max_blocks") = 0, py::arg("lanes") = "auto",
+        "The unpack kernel over several (dst, src, payload_bytes) ops; up to 32 share a launch.");
+  m.def("fill_packed", [](uintptr_t ptr, size_t payload_bytes, uint64_t seed, const std::string& fmt, uintptr_t stream) {
+        dev::launch_fill_packed(reinterpret_cast<void*>(ptr), wire_payload_arg(payload_bytes), seed, wire_format_arg(fmt),
+                                as_stream(stream));
+      }, py::arg("ptr"), py::arg("payload_bytes"), py::arg("seed"), py::arg("fmt"), py::arg("stream") = 0,
+      "Fills wire_bytes() at ptr with the wire image of bf16 operand stream `seed`.");
+  m.def("verify_unpacked", &device_verify_unpacked, py::arg("ptr"), py::arg("payload_bytes"), py::arg("seed"), py::arg("fmt"),
+        py::arg("stream") = 0,
+        "Compares the buffer with operand stream `seed` packed and unpacked: (wrong 32-bit words, checksum, first bad "
+        "byte offset or 2**64-1).");
+  m.def("host_wire_pack", [](const py::bytes& payload, const std::string& fmt) {
+        const std::string in = payload;
+        const WireFormat f = wire_format_arg(fmt);
+        std::string out(wire_bytes(wire_payload_arg(in.size()), f), '\0');
+        host_wire_pack(&out[0], in.data(), in.size(), f);
+        return py::bytes(out);
+      }, py::arg("payload"), py::arg("fmt"), "CPU pack of bf16 bytes, bit-compatible with the pack kernel.");
+  m.def("host_wire_unpack", [](const py::bytes& wire, size_t payload_bytes, const std::string& fmt) {
+        const std::string in = wire;
+        const WireFormat f = wire_format_arg(fmt);
+        if (in.size() != wire_bytes(wire_payload_arg(payload_bytes), f)) throw py::value_error("host_wire_unpack: wire_bytes() of input");
+        std::string out(payload_bytes, '\0');
+        host_wire_unpack(&out[0], in.data(), payload_bytes, f);
+        return py::bytes(out);
+      }, py::arg("wire"), py::arg("payload_bytes"), py::arg("fmt"), "CPU unpack, bit-compatible with the unpack kernel.");
   m.attr("MAX_SIGNALS") = dev::kMaxSignals;
   m.def("signal", [](const FlagList& posts, const FlagList& waits, uintptr_t status_ptr, uint64_t timeout_ticks,
                      bool release_first, uintptr_t stream, uintptr_t trap_flag) {

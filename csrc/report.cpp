@@ -226,6 +226,7 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
                             format_size(rec.bytes).c_str(), rec.cfg.iters, timing_name(rec.cfg.timing), rec.cfg.warmup,
                             rec.cfg.verify ? " verify" : "");
   if (rec.load.on()) head.insert(head.size() - 1, strfmt(" load=%s:%d", rec.load.kind.c_str(), rec.load.wgs));
+  if (rec.cfg.wire != WireFormat::Off) head.insert(head.size() - 1, strfmt(" wire=%s", wire_format_name(rec.cfg.wire)));
   std::fprintf(out, "\n== %s ==\n", head.c_str());
   bool blank_diag = rec.mode != Mode::Self && n > 1;
   auto gbs = flow_matrix_gbs(rec, n);
@@ -268,6 +269,10 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
   if (rec.cfg.reduce != ReduceType::Off)
     std::fprintf(out, "  reduce: %s, every receiver sums its own shard and its incoming messages in one launch\n",
                  reduce_type_name(rec.cfg.reduce));
+  if (rec.cfg.wire != WireFormat::Off)
+    std::fprintf(out, "  wire: %s, %llu wire bytes per %llu-byte bf16 message; rates are payload bytes (bf16 delivered)\n",
+                 wire_format_name(rec.cfg.wire), static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.wire)),
+                 static_cast<unsigned long long>(rec.cfg.bytes));
   if (verified && rec.cfg.inline_check) {
     uint64_t in_flight = 0, in_bad = 0;
     for (const auto& ph : rec.phases) {
@@ -400,6 +405,9 @@ std::string run_to_json(const RunRecord& rec, int n) {
     }
     o << ",\"reduce\":{\"dtype\":\"" << reduce_type_name(rec.cfg.reduce) << "\",\"fan_in\":" << fan_in << "}";
   }
+  if (rec.cfg.wire != WireFormat::Off)  // present only when the option is on
+    o << ",\"wire\":{\"format\":\"" << wire_format_name(rec.cfg.wire) << "\",\"payload_bytes\":" << rec.cfg.bytes
+      << ",\"wire_bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.wire) << "}";
   if (rec.cfg.inline_check) {  // present only when the option is on
     uint64_t in_flight = 0, in_bad = 0;
     std::vector<const PhaseResult*> phs;

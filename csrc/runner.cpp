@@ -136,7 +136,7 @@ std::vector<Transport::GroupFlow> group_flow_list(const Phase& phase) {
 }  // namespace
 
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen,
-                          const InlineRecords* check, ReduceType reduce) {
+                          const InlineRecords* check, ReduceType reduce, WireFormat wire) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const std::vector<int> rs = remote_slots(phase, t.rank());
   const int base = gen * std::max(1, phase.max_recv_slots());
@@ -150,11 +150,15 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
     }
     t.group_flows(bufs.send_buf(), flows, bytes);
   }
-  for (size_t j = 0; j < ops.send_to.size(); ++j) t.send_to_slot(bufs.send_at(off), bytes, ops.send_to[j], base + rs[j]);
+  // With a wire format the send region holds the packed image: that is what a send moves.
+  const size_t sent = wire == WireFormat::Off ? bytes : static_cast<size_t>(wire_bytes(bytes, wire));
+  for (size_t j = 0; j < ops.send_to.size(); ++j) t.send_to_slot(bufs.send_at(off), sent, ops.send_to[j], base + rs[j]);
   if (reduce != ReduceType::Off && !ops.recv_from.empty())
     t.reduce_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce);
   for (size_t i = 0; reduce == ReduceType::Off && i < ops.recv_from.size(); ++i) {
-    if (check)
+    if (wire != WireFormat::Off)
+      t.recv_unpacked(bufs.recv_buf(base + static_cast<int>(i)), bytes, ops.recv_from[i], off, wire);
+    else if (check)
       t.recv_checked(bufs.recv_buf(base + static_cast<int>(i)), bytes, ops.recv_from[i], off,
                      generation_seed(ops.recv_from[i], bytes, check->salt, gen), check->first + i);
     else
@@ -227,6 +231,11 @@ void prepare_payload(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
     for (int g = 0; g < gens && !(ops.send_to.empty() && ops.recv_from.empty()); ++g)
       t.fill_operand(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
                      generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.reduce);
+  } else if (cfg.wire != WireFormat::Off) {
+    // The region at a generation's usual offset holds the wire image of its stream.
+    for (int g = 0; g < gens && !ops.send_to.empty(); ++g)
+      t.fill_packed(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
+                    generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.wire);
   } else if (!ops.send_to.empty())
     for (int g = 0; g < gens; ++g)
       t.fill(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
@@ -256,6 +265,22 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
         if (g == 0) (*per_slot)[1] = v.checksum;
       }
     }
+    return bad;
+  }
+  if (cfg.wire != WireFormat::Off) {
+    // Every (generation, slot) against its sender's stream, packed and unpacked.
+    uint64_t bad = 0;
+    for (int g = 0; g < gens; ++g)
+      for (size_t i = 0; i < ops.recv_from.size(); ++i) {
+        const VerifyResult v = t.verify_unpacked(bufs.recv_buf(g * per + static_cast<int>(i)), cfg.bytes,
+                                                 generation_seed(ops.recv_from[i], cfg.bytes, cfg.salt, g), cfg.wire);
+        bad += v.mismatches;
+        if (per_job) per_job->push_back(v.mismatches);
+        if (per_slot) {
+          (*per_slot)[2 * i] += v.mismatches;
+          if (g == 0) (*per_slot)[2 * i + 1] = v.checksum;
+        }
+      }
     return bad;
   }
   std::vector<Transport::VerifyJob> jobs;
@@ -407,7 +432,7 @@ void rechunk_until_warmup_verifies(Transport& t, Bootstrap& boot, const Phase& p
     }
     boot.barrier();
     if (active) {
-      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce);
+      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire);
       t.sync();
     }
     bad = boot.allreduce_sum_u64(local_mismatches());
@@ -583,6 +608,12 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
     P2P_CHECK(cfg.bytes % 4 == 0, "reduce: the message size must be a multiple of 4");
     P2P_CHECK(!cfg.inline_check && cfg.diagnose == 0, "reduce: not with the inline check or the diagnosis");
   }
+  if (cfg.wire != WireFormat::Off) {
+    P2P_CHECK(t.supports_wire(), "wire: this transport cannot unpack a wire image (ipc with the kernel engine, or host)");
+    P2P_CHECK(cfg.bytes % kWireBlockBytes == 0, "wire: the message size must be a multiple of 64");
+    P2P_CHECK(cfg.reduce == ReduceType::Off && !cfg.inline_check && cfg.diagnose == 0,
+              "wire: not with reduce, the inline check or the diagnosis");
+  }
   // Relay ranks of a multi-path transport post (and time) the phase too; a
   // flow is still charged by its two endpoints only.
   const bool active = posts_phase(t, phase, me);
@@ -604,7 +635,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   const double hooked0 = now_seconds();
   if (cfg.before_timing) cfg.before_timing();
   if (active) {
-    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce);
+    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire);
     t.sync();
   }
   if (cfg.verify && cfg.warmup > 0) {
@@ -648,7 +679,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   auto post = [&](int i) {
     if (skip_some) t.set_discard(i % 2 == 0);
     const InlineRecords rec{static_cast<size_t>(i) * nrecv, cfg.salt};
-    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce);
+    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire);
   };
 
   double my_seconds = 0;

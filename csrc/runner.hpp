@@ -78,6 +78,15 @@ struct RunConfig {
   // slot 0 with the regenerated sum and charges it to the rank's first flow.
   // Off: nothing changes.
   ReduceType reduce = ReduceType::Off;
+  // Block-scaled wire format (--wire; transport.hpp recv_unpacked): payloads
+  // are bf16 operand streams (wire_op.hpp), a generation's send region holds
+  // the MXFP8 / MXFP4 image of its stream at the usual offset (the image is
+  // smaller than the payload: same slot_stride, same exported block), and
+  // every receive is posted as recv_unpacked.  Flows are timed and reported in
+  // payload bytes, the bf16 delivered; the check after timing compares every
+  // kept slot with its sender's stream packed and unpacked.  Off: nothing
+  // changes.
+  WireFormat wire = WireFormat::Off;
   // Hooks around what a phase measures (--load brackets it with a background
   // load): run_phase calls them on every rank of a non-idle phase, in both
   // timings.  before_timing: after the payload and the poison are posted,
@@ -227,10 +236,12 @@ struct InlineRecords {
   size_t first = 0;
   uint64_t salt = 0;
 };
-// With `reduce`, the receives are posted as one Transport::reduce_from into
+// With `wire`, sends move the packed image and the receives are posted as
+// Transport::recv_unpacked.  With `reduce`, the receives are posted as one Transport::reduce_from into
 // slot gen * phase.max_recv_slots(), the local operand being send region gen.
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0,
-                          const InlineRecords* check = nullptr, ReduceType reduce = ReduceType::Off);
+                          const InlineRecords* check = nullptr, ReduceType reduce = ReduceType::Off,
+                          WireFormat wire = WireFormat::Off);
 
 // Receive generations for verified runs of messages up to `max_bytes` with
 // `slots` receive slots per iteration and up to `iters` iterations: as many as

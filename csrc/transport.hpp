@@ -28,6 +28,7 @@
 #include "diagnose.hpp"
 #include "prng.hpp"
 #include "reduce_op.hpp"
+#include "wire_op.hpp"
 
 namespace p2p {
 
@@ -131,6 +132,27 @@ class Transport {
                            size_t /*src_offset*/, ReduceType /*dtype*/) {}
   virtual VerifyResult verify_reduced(const void* /*p*/, size_t /*bytes*/, const std::vector<uint64_t>& /*seeds*/,
                                       ReduceType /*dtype*/) {
+    return {};
+  }
+
+  // ---- block-scaled wire formats (--wire; wire_op.hpp) ----
+  // The payload is bf16, the link carries its MXFP8 / MXFP4 image: a send
+  // region holds wire_bytes(payload_bytes) of packed data, and the receiver
+  // widens it to payload_bytes of bf16 as it pulls.
+  //   fill_packed     the wire image of operand stream `seed` into a send region;
+  //   recv_unpacked   recv_from, reading the peer's wire image at `src_offset`
+  //                   and storing bf16 to dst (a registered receive slot);
+  //                   inside a group.  The IPC pull engine does it in its
+  //                   gfx950 unpack kernel, one launch per group; the host
+  //                   transport receives the image and widens it on the CPU.
+  //                   The matching send moves wire_bytes(payload_bytes).
+  //   verify_unpacked blocking: p against the stream packed and unpacked by
+  //                   the shared function, a wrong 32-bit word counted once.
+  virtual bool supports_wire() const { return false; }
+  virtual void fill_packed(void* /*p*/, size_t /*payload_bytes*/, uint64_t /*seed*/, WireFormat /*fmt*/) {}
+  virtual void recv_unpacked(void* /*dst*/, size_t /*payload_bytes*/, int /*peer*/, size_t /*src_offset*/,
+                             WireFormat /*fmt*/) {}
+  virtual VerifyResult verify_unpacked(const void* /*p*/, size_t /*payload_bytes*/, uint64_t /*seed*/, WireFormat /*fmt*/) {
     return {};
   }
 

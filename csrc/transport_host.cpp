@@ -101,6 +101,93 @@ VerifyResult host_verify_reduced(const void* p, size_t bytes, const uint64_t* se
   return r;
 }
 
+// ---- block-scaled wire formats (wire_op.hpp): tile by tile, block by block ----
+namespace {
+
+// Calls fn(block's payload offset, block's element bytes offset, scale byte offset) for every block.
+template <typename Fn>
+void for_each_wire_block(size_t n, WireFormat f, Fn fn) {
+  const uint32_t eb = wire_block_elem_bytes(f);
+  size_t wire_at = 0;
+  for (size_t tile = 0; tile * kWireTilePayload < n; ++tile) {
+    const uint32_t nb = static_cast<uint32_t>(std::min<size_t>(kWireTileBlocks, (n - tile * kWireTilePayload) / kWireBlockBytes));
+    for (uint32_t b = 0; b < nb; ++b)
+      fn(tile * kWireTilePayload + b * kWireBlockBytes, wire_at + b * eb, wire_at + nb * eb + b);
+    wire_at += wire_tile_bytes(nb, f);
+  }
+}
+
+void check_wire(size_t n, WireFormat f, const char* who) {
+  P2P_CHECK(f == WireFormat::Mxfp8 || f == WireFormat::Mxfp4, std::string(who) + ": the format is mxfp8 or mxfp4");
+  P2P_CHECK(n % kWireBlockBytes == 0, std::string(who) + ": the payload is a multiple of 64 bytes (blocks of 32 bf16)");
+}
+
+// Block `block` (counted from the payload's start) of operand stream `seed`.
+void wire_operand_block(uint64_t seed, uint64_t block, uint16_t* x) {
+  for (uint32_t j = 0; j < 16; ++j) {
+    const uint64_t i = block * 16 + j;
+    const uint32_t w = wire_operand_word(prng_word(seed, i), i);
+    x[2 * j] = static_cast<uint16_t>(w);
+    x[2 * j + 1] = static_cast<uint16_t>(w >> 16);
+  }
+}
+
+}  // namespace
+
+void host_wire_pack(void* wire, const void* payload, size_t n, WireFormat f) {
+  check_wire(n, f, "host_wire_pack");
+  std::memset(wire, 0, wire_bytes(n, f));  // the padding
+  auto* out = static_cast<uint8_t*>(wire);
+  for_each_wire_block(n, f, [&](size_t at, size_t elems, size_t scale) {
+    uint16_t x[kWireBlockElems];
+    std::memcpy(x, static_cast<const char*>(payload) + at, sizeof(x));
+    wire_pack_block(x, out + elems, out + scale, f);
+  });
+}
+
+void host_wire_unpack(void* payload, const void* wire, size_t n, WireFormat f) {
+  check_wire(n, f, "host_wire_unpack");
+  const auto* in = static_cast<const uint8_t*>(wire);
+  for_each_wire_block(n, f, [&](size_t at, size_t elems, size_t scale) {
+    uint16_t x[kWireBlockElems];
+    wire_unpack_block(in + elems, in[scale], x, f);
+    std::memcpy(static_cast<char*>(payload) + at, x, sizeof(x));
+  });
+}
+
+void host_fill_packed(void* wire, size_t n, uint64_t seed, WireFormat f) {
+  check_wire(n, f, "host_fill_packed");
+  std::memset(wire, 0, wire_bytes(n, f));
+  auto* out = static_cast<uint8_t*>(wire);
+  for_each_wire_block(n, f, [&](size_t at, size_t elems, size_t scale) {
+    uint16_t x[kWireBlockElems];
+    wire_operand_block(seed, at / kWireBlockBytes, x);
+    wire_pack_block(x, out + elems, out + scale, f);
+  });
+}
+
+VerifyResult host_verify_unpacked(const void* p, size_t n, uint64_t seed, WireFormat f) {
+  check_wire(n, f, "host_verify_unpacked");
+  VerifyResult r;
+  for (size_t at = 0; at < n; at += kWireBlockBytes) {
+    uint16_t x[kWireBlockElems], want[kWireBlockElems];
+    uint8_t elems[32], scale;
+    wire_operand_block(seed, at / kWireBlockBytes, x);
+    wire_pack_block(x, elems, &scale, f);
+    wire_unpack_block(elems, scale, want, f);
+    for (uint32_t j = 0; j < 16; ++j) {
+      uint32_t got;
+      std::memcpy(&got, static_cast<const char*>(p) + at + 4 * j, 4);
+      r.checksum += got;
+      if (got != (want[2 * j] | static_cast<uint32_t>(want[2 * j + 1]) << 16)) {
+        if (!r.mismatches) r.first_bad = at + 4 * j;
+        ++r.mismatches;
+      }
+    }
+  }
+  return r;
+}
+
 namespace {
 
 void sockopts(int fd) {
@@ -219,11 +306,28 @@ class HostTransport final : public Transport {
     }
   }
 
+  // ---- wire formats: the packed image travels, the CPU widens it ----
+  bool supports_wire() const override { return true; }
+  void fill_packed(void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt) override {
+    host_fill_packed(p, payload_bytes, seed, fmt);
+  }
+  VerifyResult verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt) override {
+    return host_verify_unpacked(p, payload_bytes, seed, fmt);
+  }
+  void recv_unpacked(void* dst, size_t payload_bytes, int peer, size_t, WireFormat fmt) override {
+    P2P_CHECK(in_group_, "host transport: recv_unpacked inside a group");
+    P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
+    // Moving a vector keeps its storage: the op's pointer stays good as unpacks_ grows.
+    unpacks_.push_back({dst, payload_bytes, fmt, std::vector<char>(wire_bytes(payload_bytes, fmt))});
+    ops_.push_back({false, peer, unpacks_.back().wire.data(), unpacks_.back().wire.size()});
+  }
+
   void group_begin() override {
     P2P_CHECK(!in_group_, "nested group");
     in_group_ = true;
     ops_.clear();
     reduce_ = {};
+    unpacks_.clear();
   }
   void send(const void* p, size_t bytes, int peer) override {
     P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
@@ -251,6 +355,10 @@ class HostTransport final : public Transport {
       host_reduce(reduce_.dst, operands.data(), static_cast<int>(operands.size()), reduce_.bytes, reduce_.dtype);
     }
     reduce_ = {};
+    // Injected skip fault: the images were read off the wire and are dropped.
+    for (const PendingUnpack& u : unpacks_)
+      if (!discarding()) host_wire_unpack(u.dst, u.wire.data(), u.bytes, u.fmt);
+    unpacks_.clear();
   }
 
   int mark() override {
@@ -268,6 +376,12 @@ class HostTransport final : public Transport {
     const void* local_src = nullptr;
     ReduceType dtype = ReduceType::Off;
     size_t npeers = 0;
+  };
+  struct PendingUnpack {
+    void* dst;
+    size_t bytes;  // payload
+    WireFormat fmt;
+    std::vector<char> wire;
   };
   struct Op {
     bool is_send;
@@ -373,6 +487,7 @@ class HostTransport final : public Transport {
   std::vector<Op> ops_;
   PendingReduce reduce_;       // the open group's reduce_from, summed in group_end()
   std::vector<char> scratch_;  // its incoming messages, one after the other
+  std::vector<PendingUnpack> unpacks_;  // the open group's recv_unpacked, widened in group_end()
   std::vector<double> marks_;
 };
 

@@ -195,6 +195,7 @@ class IpcTransport final : public GpuTransport {
     ops_.clear();
     checked_ops_.clear();
     reduce_ = {};
+    unpack_ops_.clear();
     if (plan_) plan_->group_begin();
   }
 
@@ -286,6 +287,30 @@ class IpcTransport final : public GpuTransport {
       reduce_.srcs.push_back(static_cast<const char*>(reg->peer_send.ptr[static_cast<size_t>(peer)]) + src_offset);
       reduce_.coherent.push_back(peer != rank_);
     }
+  }
+
+  // ---- wire formats (transport.hpp): the pull engine's unpack kernel reads
+  // the peers' MXFP8 / MXFP4 images and stores bf16, one launch per group.
+  bool supports_wire() const override { return engine_ == "kernel"; }
+  void recv_unpacked(void* dst, size_t payload_bytes, int peer, size_t src_offset, WireFormat fmt) override {
+    P2P_CHECK(supports_wire(), "ipc transport: --wire needs --ipc-engine kernel");
+    P2P_CHECK(in_group_, "ipc transport: recv_unpacked inside a group");
+    P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
+    P2P_CHECK(unpack_ops_.empty() || fmt == unpack_fmt_, "ipc transport: one wire format per group");
+    const Registration* reg = nullptr;
+    for (const auto& r : regs_)
+      if (slot_of(r, dst) >= 0 && payload_bytes <= r.slot_bytes) reg = &r;
+    P2P_CHECK(reg, "ipc transport unpacks only into a registered receive slot");
+    P2P_CHECK(src_offset + wire_bytes(payload_bytes, fmt) <= reg->send_bytes,
+              "ipc transport: wire image beyond the peer's send buffer");
+    if (discarding()) return;  // injected skip fault: the pull is not issued
+    unpack_fmt_ = fmt;
+    dev::UnpackOp op;
+    op.dst = dst;
+    op.src = static_cast<const char*>(reg->peer_send.ptr[static_cast<size_t>(peer)]) + src_offset;
+    op.payload_bytes = payload_bytes;
+    op.coherent = peer != rank_;
+    unpack_ops_.push_back(op);
   }
 
   void group_end() override {
@@ -441,6 +466,10 @@ class IpcTransport final : public GpuTransport {
       dev::launch_reduce_wide(reduce_.dst, reduce_.bytes, reduce_.srcs.data(), reduce_.coherent.data(),
                               static_cast<int>(reduce_.srcs.size()), false, reduce_.dtype, stream_, 0, partial_);
       reduce_ = {};
+    }
+    if (!unpack_ops_.empty()) {
+      dev::launch_multi_unpack(unpack_ops_.data(), static_cast<int>(unpack_ops_.size()), unpack_fmt_, stream_);
+      unpack_ops_.clear();
     }
     if (!checked_ops_.empty()) {
       dev::launch_multi_copy_checked(checked_ops_.data(), static_cast<int>(checked_ops_.size()), stream_);
@@ -607,6 +636,9 @@ class IpcTransport final : public GpuTransport {
     std::vector<const void*> srcs;   // operand 0: the own shard
     std::vector<unsigned char> coherent;  // per source: a peer's mapped buffer
   } reduce_;
+  // Pull kernel: the open group's recv_unpacked ops, launched in flush().
+  std::vector<dev::UnpackOp> unpack_ops_;
+  WireFormat unpack_fmt_ = WireFormat::Off;
   void* partial_ = nullptr;  // f32 planes of a wide bf16 sum (kernels.hpp reduce_partial_bytes)
   size_t partial_bytes_ = 0;
 

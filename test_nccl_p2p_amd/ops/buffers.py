@@ -265,6 +265,102 @@ def words_to_bytes(w: torch.Tensor) -> torch.Tensor:
     return torch.stack([(w >> (8 * k)) & 0xFF for k in range(4)], dim=1).to(torch.uint8).reshape(-1)
 
 
+# ------------------------------------------------------ block-scaled wire ----
+
+# Per format: stored mantissa bits, exponent of the smallest normal, the
+# maximum as (significand, exponent), the sign's bit and a block's element bytes.
+WIRE_FORMATS = {"mxfp8": dict(mbits=3, emin=-6, top=1.75, emax=8, sign=7, block_bytes=32),
+                "mxfp4": dict(mbits=1, emin=0, top=1.5, emax=2, sign=3, block_bytes=16)}
+WIRE_TILE_BLOCKS = 128
+
+
+def wire_pack_(dst: torch.Tensor, src: torch.Tensor, fmt: str, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """The bytes of ``src`` read as bf16 (a multiple of 64 bytes) -> their
+    'mxfp8' / 'mxfp4' wire image in ``dst`` with the gfx950 pack kernel."""
+    nbytes = _check_tensor(src)
+    nat = require_native()
+    if _check_tensor(dst) < nat.wire_bytes(nbytes, fmt):
+        raise ValueError("wire_pack_: dst holds less than wire_bytes() of src")
+    nat.wire_pack(dst.data_ptr(), src.data_ptr(), nbytes, fmt, _stream(stream))
+    return dst
+
+
+def wire_unpack_(dst: torch.Tensor, src: torch.Tensor, fmt: str, *, coherent: bool = False, max_blocks: int = 0,
+                 lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """The wire image in ``src`` -> the bytes of ``dst`` as bf16 with the
+    gfx950 unpack kernel (the IPC pull engine's receive under ``--wire``)."""
+    nbytes = _check_tensor(dst)
+    nat = require_native()
+    if _check_tensor(src) < nat.wire_bytes(nbytes, fmt):
+        raise ValueError("wire_unpack_: src holds less than wire_bytes() of dst")
+    nat.wire_unpack(dst.data_ptr(), src.data_ptr(), nbytes, fmt, _stream(stream), coherent, max_blocks, lanes)
+    return dst
+
+
+def reference_wire_operands(nbytes: int, seed: int, device="cpu") -> torch.Tensor:
+    """The first ``nbytes`` (a multiple of 64) of bf16 operand stream ``seed``
+    as int64 words: sign and mantissa of both halves of the PRNG word, the
+    exponent field 64 + (block & 31) + the low 4 bits of the half's own."""
+    assert nbytes % 64 == 0
+    w = reference_words(0, nbytes // 4, seed, device)
+    block = (torch.arange(nbytes // 4, dtype=torch.int64, device=w.device) >> 4) & 31
+
+    def half(h):
+        return (h & 0x807F) | ((64 + block + ((h >> 7) & 15)) << 7)
+
+    return half(w & 0xFFFF) | (half(w >> 16) << 16)
+
+
+def _pow2(k: torch.Tensor) -> torch.Tensor:
+    return torch.pow(torch.tensor(2.0, dtype=torch.float64), k.to(torch.float64))
+
+
+def _wire_quantize(words: torch.Tensor, fmt: str):
+    """Per block of 32 elements, in float64 (amax, the division by the scale
+    and the grid are exact there): the scale bytes [blocks], the element codes
+    [blocks, 32] and the values they stand for, scale applied."""
+    f = WIRE_FORMATS[fmt]
+    words = words.cpu()
+    h = torch.stack([words & 0xFFFF, words >> 16], dim=1).reshape(-1, 32)
+    x = _words_to_f32((h << 16) & M32).to(torch.float64)
+    amax = x.abs().amax(dim=1)
+    m, ex = torch.frexp(amax)  # amax = 2m x 2^(ex - 1), 2m in [1, 2)
+    e = ex.to(torch.int64) - 1 - f["emax"] + (2 * m > f["top"]).to(torch.int64)  # the no-clip rule
+    sb = torch.where(amax == 0, torch.full_like(e, 127), (e + 127).clamp(1, 254))
+    scale = _pow2(sb - 127)[:, None]
+    q = x.abs() / scale
+    qe = torch.frexp(q)[1].to(torch.int64) - 1
+    step = _pow2(qe.clamp(min=f["emin"]) - f["mbits"])  # the grid's spacing at q, subnormals included
+    r = torch.round(q / step) * step  # ties to even
+    re = torch.frexp(r)[1].to(torch.int64) - 1
+    normal = ((re - f["emin"] + 1) << f["mbits"]) + ((r / _pow2(re) - 1) * 2 ** f["mbits"]).to(torch.int64)
+    code = torch.where(r >= 2.0 ** f["emin"], normal, (r * 2.0 ** (f["mbits"] - f["emin"])).to(torch.int64))
+    neg = torch.signbit(x)
+    value = r * scale
+    return sb, code | (neg.to(torch.int64) << f["sign"]), torch.where(neg, -value, value)
+
+
+def reference_wire_pack(words: torch.Tensor, fmt: str) -> torch.Tensor:
+    """The wire image (uint8) of the bf16 payload ``words`` (int64 words, 16
+    per block): per tile of up to 128 blocks the element bytes, the scale
+    bytes and zeros up to a multiple of 16."""
+    sb, code, _ = _wire_quantize(words, fmt)
+    elems = code if fmt == "mxfp8" else code[:, 0::2] | (code[:, 1::2] << 4)
+    parts = []
+    for t in range(0, sb.numel(), WIRE_TILE_BLOCKS):
+        tile = torch.cat([elems[t:t + WIRE_TILE_BLOCKS].reshape(-1), sb[t:t + WIRE_TILE_BLOCKS]])
+        parts += [tile, torch.zeros(-tile.numel() % 16, dtype=torch.int64)]
+    return torch.cat(parts).to(torch.uint8)
+
+
+def reference_wire_roundtrip(words: torch.Tensor, fmt: str) -> torch.Tensor:
+    """What the receiver holds (uint8, bf16 payload bytes): every element
+    quantised under its block's scale and widened again, exactly."""
+    value = _wire_quantize(words, fmt)[2].to(torch.float32).reshape(-1)
+    bits = (value.view(torch.int32).to(torch.int64) >> 16) & 0xFFFF
+    return torch.stack([bits & 0xFF, bits >> 8], dim=1).to(torch.uint8).reshape(-1)
+
+
 # ---------------------------------------------------------------- diagnosis --
 
 class GranuleRecord(NamedTuple):
