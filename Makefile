@@ -26,7 +26,7 @@ HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
 CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o reduce.o wire.o diagnose_hip.o pingpong.o stream.o load_hip.o)
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o reduce.o wire.o wire_reduce.o diagnose_hip.o pingpong.o stream.o load_hip.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in
@@ -107,6 +107,10 @@ $(BUILD)/gpu/reduce.o: csrc/reduce.hip $(HEADERS) | $(BUILD)/gpu
 # The wire-format kernels convert with the scaled conversion instructions and
 # integer arithmetic only: no packed f32 instructions in this object either.
 $(BUILD)/gpu/wire.o: csrc/wire.hip $(HEADERS) | $(BUILD)/gpu
+	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
+# The sum of wire images keeps its 16 add chains per lane scalar too.
+$(BUILD)/gpu/wire_reduce.o: csrc/wire_reduce.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
 # csrc/diagnose.cpp (host side, in CORE) owns diagnose.o.

@@ -141,6 +141,15 @@ data
                          bytes (the bf16 delivered); every kept slot is checked bit for bit.
                          --transport ipc --ipc-engine kernel, or host; sizes multiples of 64;
                          not with --reduce, --verify-inline, --diagnose, --reference or --resume
+      --reduce-wire FORMAT  mxfp8 | mxfp4, with --reduce bf16: every operand of a receiver's
+                         sum is a block-scaled wire image (as --wire carries), its own shard
+                         included.  The link moves the images; one launch of the gfx950
+                         wire-reduce kernel dequantises them, adds them in f32 in operand
+                         order and stores the sum as bf16, rounded once: the widened copies
+                         never exist.  At most 8 operands (own + 7 incoming).  Flows are
+                         timed and reported in payload bytes, the sum is checked bit for bit.
+                         --transport ipc --ipc-engine kernel, or host; sizes multiples of 64;
+                         not with --wire, --verify-inline, --diagnose, --reference or --resume
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -292,7 +301,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
                                     "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load", "--stream-sizes",
-                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire"};
+                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire", "--reduce-wire"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -401,6 +410,13 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       const std::string v = next();
       if (!parse_wire_format(v, &cfg->run.wire) || cfg->run.wire == WireFormat::Off) {
         std::fprintf(stderr, "p2p_matrix: --wire '%s': the format is mxfp8 or mxfp4\n", v.c_str());
+        *exit_code = 1;
+        return false;
+      }
+    } else if (a == "--reduce-wire") {
+      const std::string v = next();
+      if (!parse_wire_format(v, &cfg->run.reduce_wire) || cfg->run.reduce_wire == WireFormat::Off) {
+        std::fprintf(stderr, "p2p_matrix: --reduce-wire '%s': the format is mxfp8 or mxfp4\n", v.c_str());
         *exit_code = 1;
         return false;
       }
@@ -544,6 +560,38 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       return false;
     }
   }
+  // --reduce-wire: the sum of --reduce bf16 over operands that arrive as wire
+  // images; only where a data plane can do both at once (the pull engine's
+  // wire-reduce kernel, the host transport's CPU sum), on whole blocks of 32
+  // bf16.  Checked before --reduce, whose refusals would name that option.
+  if (cfg->run.reduce_wire != WireFormat::Off) {
+    std::string why;
+    if (cfg->run.reduce == ReduceType::Off)
+      why = "needs --reduce bf16: it says how the operands of that sum arrive";
+    else if (cfg->run.reduce != ReduceType::Bf16)
+      why = strfmt("needs --reduce bf16, not %s: the format's payload is bf16", reduce_type_name(cfg->run.reduce));
+    if (why.empty() && cfg->run.wire != WireFormat::Off)
+      why = "cannot be combined with --wire: that option stores every widened message, this one only their sum";
+    if (why.empty() && !(cfg->transport == "host" || (cfg->transport == "ipc" && cfg->ipc_engine == "kernel")))
+      why = strfmt("needs --transport ipc --ipc-engine kernel (the gfx950 wire-reduce kernel) or --transport host; %s%s%s sums no wire images",
+                   cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",
+                   cfg->transport == "ipc" ? cfg->ipc_engine.c_str() : "");
+    for (size_t b : cfg->sizes)
+      if (why.empty() && b % kWireBlockBytes) why = strfmt("scales blocks of 32 bf16: size %zu is not a multiple of 64", b);
+    if (why.empty() && cfg->run.inline_check)
+      why = "cannot be combined with --verify-inline: that check compares a copied message with the raw stream";
+    if (why.empty() && cfg->run.diagnose > 0)
+      why = "cannot be combined with --diagnose: the diagnosis explains a slot by one sender's raw streams";
+    if (why.empty() && cfg->reference_buffers)  // set by --reference alone
+      why = "cannot be combined with --reference: that is the reference's run, which only moves its payload";
+    if (why.empty() && cfg->resume)
+      why = "cannot be combined with --resume: the runs in the file are counted by mode, direction and size alone";
+    if (!why.empty()) {
+      std::fprintf(stderr, "p2p_matrix: --reduce-wire %s\n", why.c_str());
+      *exit_code = 1;
+      return false;
+    }
+  }
   // --reduce: only where a data plane can sum (the pull engine's reduce kernel,
   // the host transport's CPU sum), on whole 32-bit words, and not beside the
   // options that read a receive slot as one sender's stream.
@@ -581,7 +629,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     for (size_t b : cfg->sizes)
       if (why.empty() && b % kWireBlockBytes) why = strfmt("scales blocks of 32 bf16: size %zu is not a multiple of 64", b);
     if (why.empty() && cfg->run.reduce != ReduceType::Off)
-      why = "cannot be combined with --reduce: the reduce kernel sums unpacked operands";
+      why = "cannot be combined with --reduce: the reduce kernel sums unpacked operands (--reduce-wire sums wire images)";
     if (why.empty() && cfg->run.inline_check)
       why = "cannot be combined with --verify-inline: that check compares a copied message with the raw stream";
     if (why.empty() && cfg->run.diagnose > 0)

@@ -86,6 +86,11 @@ class DeviceChecks {
   VerifyResult verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt, hipStream_t stream,
                                const StreamWait& wait);
 
+  // ---- sum of wire images (Transport::verify_reduced_unpacked; kernels.hpp launch_verify_wire_reduced) ----
+  // Blocking: reset + the check + finalize + readback.
+  VerifyResult verify_wire_reduced(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds, WireFormat fmt,
+                                   hipStream_t stream, const StreamWait& wait);
+
   // ---- batched verify (Transport::verify_many) ----
   // One buffer at a time under --verify-impl stride or P2P_VERIFY_BATCH=0.
   std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs, hipStream_t stream, const StreamWait& wait);

@@ -30,6 +30,9 @@
 //   wire    — block-scaled payloads for the IPC transport (--wire, wire.hip):
 //             the receive that widens MXFP8 / MXFP4 to bf16 as it pulls, the
 //             sender's pack, and the check of an unpacked buffer
+//   wsum    — receive-and-reduce of wire images (--reduce-wire, wire_reduce.hip):
+//             K MXFP8 / MXFP4 images summed in f32 into bf16 in one launch,
+//             and the check of such a sum
 //
 // Measured on MI355X (profiles/, scripts/fill_probe.hip): streaming at one
 // 16 B access per lane with one block per 4 KiB (a "full grid", up to 2^20
@@ -46,6 +49,7 @@
 #include "prng.hpp"
 #include "reduce_op.hpp"
 #include "wire_op.hpp"
+#include "wire_reduce_op.hpp"
 
 namespace p2p {
 namespace dev {
@@ -247,6 +251,38 @@ void launch_fill_packed(void* wire, size_t payload_bytes, uint64_t seed, WireFor
 // in acc[0] like launch_verify's (reset acc first).  Never inside timing.
 void launch_verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt, VerifyAccum* acc,
                             hipStream_t stream);
+
+// ---- receive-and-reduce of wire images (wire_reduce.hip; --reduce-wire) ----
+// The pull engine's fourth data plane: every one of the nsrc sources is the
+// MXFP8 / MXFP4 wire image of payload_bytes of bf16, and dst receives
+// payload_bytes of bf16, the sum of the dequantised operands in source order
+// (wire_reduce_op.hpp: f32 add chain, one rounding).  One op per launch, as
+// the engine posts one reduce per group.  A 256-thread workgroup takes whole
+// tiles, 16 elements per lane; a lane issues the nsrc element loads and scale
+// byte loads of a tile before its first conversion (nsrc is a template
+// parameter dispatched on the host), keeps 16 f32 accumulators and ends in two
+// 16 B non-temporal stores to dst (local memory).  Bit k of coherent_mask:
+// source k is a hipIpc-mapped peer buffer, read with system-scope (sc0 sc1)
+// raw-buffer loads through one range-checked descriptor per tile; other
+// sources use non-temporal loads.  payload_bytes is a multiple of 64, buffers
+// are 16 B aligned, nsrc is 1..8 (a P2P_CHECK each).  max_blocks > 0 caps the
+// grid and the kernel strides; `lanes` as in launch_multi_unpack, Auto being
+// the mapping measured faster for the format and fan-in.
+struct WireReduceOp {
+  void* dst = nullptr;
+  size_t payload_bytes = 0;
+  int nsrc = 0;
+  const void* src[kMaxWireReduceSrcs] = {};
+  uint32_t coherent_mask = 0;
+};
+void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks = 0,
+                        WireLanes lanes = WireLanes::Auto);
+// Regenerates the nseeds (<= kMaxWireReduceSrcs) operand streams, packs and
+// unpacks each per block (4 lanes each), sums them with reduce_op.hpp's
+// functions and compares with p word by word; the totals end in acc[0] like
+// launch_verify's (reset acc first).  Never inside timing.
+void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint64_t* seeds, int nseeds, WireFormat fmt,
+                                VerifyAccum* acc, hipStream_t stream);
 
 // ---- device-initiated ping-pong (pingpong.hip) ----
 // One wave per role.  The leader writes message i (payload words = base+i+1,

@@ -227,6 +227,8 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
                             rec.cfg.verify ? " verify" : "");
   if (rec.load.on()) head.insert(head.size() - 1, strfmt(" load=%s:%d", rec.load.kind.c_str(), rec.load.wgs));
   if (rec.cfg.wire != WireFormat::Off) head.insert(head.size() - 1, strfmt(" wire=%s", wire_format_name(rec.cfg.wire)));
+  if (rec.cfg.reduce_wire != WireFormat::Off)
+    head.insert(head.size() - 1, strfmt(" reduce-wire=%s", wire_format_name(rec.cfg.reduce_wire)));
   std::fprintf(out, "\n== %s ==\n", head.c_str());
   bool blank_diag = rec.mode != Mode::Self && n > 1;
   auto gbs = flow_matrix_gbs(rec, n);
@@ -266,7 +268,14 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
     std::fprintf(out, "  verification: %s (%llu mismatching words; %llu of %llu timed deliveries checked)\n",
                  bad ? "FAILED" : "OK", static_cast<unsigned long long>(bad), static_cast<unsigned long long>(checked),
                  static_cast<unsigned long long>(timed));
-  if (rec.cfg.reduce != ReduceType::Off)
+  if (rec.cfg.reduce_wire != WireFormat::Off)
+    std::fprintf(out,
+                 "  reduce: %s over %s images, every receiver sums its own image and its incoming ones in one launch; "
+                 "%llu wire bytes per %llu-byte bf16 message, rates are payload bytes\n",
+                 reduce_type_name(rec.cfg.reduce), wire_format_name(rec.cfg.reduce_wire),
+                 static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)),
+                 static_cast<unsigned long long>(rec.cfg.bytes));
+  else if (rec.cfg.reduce != ReduceType::Off)
     std::fprintf(out, "  reduce: %s, every receiver sums its own shard and its incoming messages in one launch\n",
                  reduce_type_name(rec.cfg.reduce));
   if (rec.cfg.wire != WireFormat::Off)
@@ -403,7 +412,11 @@ std::string run_to_json(const RunRecord& rec, int n) {
       std::vector<size_t> into(static_cast<size_t>(n), 0);
       for (const auto& f : ph.flows) fan_in = std::max(fan_in, ++into[static_cast<size_t>(f.flow.dst)] + 1);
     }
-    o << ",\"reduce\":{\"dtype\":\"" << reduce_type_name(rec.cfg.reduce) << "\",\"fan_in\":" << fan_in << "}";
+    o << ",\"reduce\":{\"dtype\":\"" << reduce_type_name(rec.cfg.reduce) << "\",\"fan_in\":" << fan_in;
+    if (rec.cfg.reduce_wire != WireFormat::Off)  // --reduce-wire: how the operands arrive
+      o << ",\"wire\":{\"format\":\"" << wire_format_name(rec.cfg.reduce_wire) << "\",\"payload_bytes\":" << rec.cfg.bytes
+        << ",\"wire_bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire) << "}";
+    o << "}";
   }
   if (rec.cfg.wire != WireFormat::Off)  // present only when the option is on
     o << ",\"wire\":{\"format\":\"" << wire_format_name(rec.cfg.wire) << "\",\"payload_bytes\":" << rec.cfg.bytes

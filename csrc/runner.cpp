@@ -136,7 +136,7 @@ std::vector<Transport::GroupFlow> group_flow_list(const Phase& phase) {
 }  // namespace
 
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen,
-                          const InlineRecords* check, ReduceType reduce, WireFormat wire) {
+                          const InlineRecords* check, ReduceType reduce, WireFormat wire, WireFormat reduce_wire) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const std::vector<int> rs = remote_slots(phase, t.rank());
   const int base = gen * std::max(1, phase.max_recv_slots());
@@ -151,9 +151,12 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
     t.group_flows(bufs.send_buf(), flows, bytes);
   }
   // With a wire format the send region holds the packed image: that is what a send moves.
-  const size_t sent = wire == WireFormat::Off ? bytes : static_cast<size_t>(wire_bytes(bytes, wire));
+  const WireFormat image = wire != WireFormat::Off ? wire : reduce_wire;
+  const size_t sent = image == WireFormat::Off ? bytes : static_cast<size_t>(wire_bytes(bytes, image));
   for (size_t j = 0; j < ops.send_to.size(); ++j) t.send_to_slot(bufs.send_at(off), sent, ops.send_to[j], base + rs[j]);
-  if (reduce != ReduceType::Off && !ops.recv_from.empty())
+  if (reduce_wire != WireFormat::Off && !ops.recv_from.empty())
+    t.reduce_unpacked_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce_wire);
+  else if (reduce != ReduceType::Off && !ops.recv_from.empty())
     t.reduce_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce);
   for (size_t i = 0; reduce == ReduceType::Off && i < ops.recv_from.size(); ++i) {
     if (wire != WireFormat::Off)
@@ -227,7 +230,12 @@ void prepare_payload(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
   P2P_CHECK(cfg.bytes <= bufs.capacity(), "message larger than buffers");
   P2P_CHECK(static_cast<int>(ops.recv_from.size()) <= bufs.slots(), "not enough receive slots");
   // With --reduce a receiver's own send region is operand 0 of its sum.
-  if (cfg.reduce != ReduceType::Off) {
+  if (cfg.reduce_wire != WireFormat::Off) {
+    // Every operand is a wire image, the receiver's own (operand 0) included.
+    for (int g = 0; g < gens && !(ops.send_to.empty() && ops.recv_from.empty()); ++g)
+      t.fill_packed(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
+                    generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.reduce_wire);
+  } else if (cfg.reduce != ReduceType::Off) {
     for (int g = 0; g < gens && !(ops.send_to.empty() && ops.recv_from.empty()); ++g)
       t.fill_operand(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
                      generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.reduce);
@@ -256,7 +264,9 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
     for (int g = 0; g < gens && !ops.recv_from.empty(); ++g) {
       std::vector<uint64_t> seeds{generation_seed(t.rank(), cfg.bytes, cfg.salt, g)};
       for (int peer : ops.recv_from) seeds.push_back(generation_seed(peer, cfg.bytes, cfg.salt, g));
-      const VerifyResult v = t.verify_reduced(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce);
+      const VerifyResult v = cfg.reduce_wire != WireFormat::Off
+                                 ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire)
+                                 : t.verify_reduced(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce);
       bad += v.mismatches;
       if (per_job)
         for (size_t i = 0; i < ops.recv_from.size(); ++i) per_job->push_back(i ? 0 : v.mismatches);
@@ -432,7 +442,7 @@ void rechunk_until_warmup_verifies(Transport& t, Bootstrap& boot, const Phase& p
     }
     boot.barrier();
     if (active) {
-      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire);
+      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire);
       t.sync();
     }
     bad = boot.allreduce_sum_u64(local_mismatches());
@@ -608,6 +618,18 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
     P2P_CHECK(cfg.bytes % 4 == 0, "reduce: the message size must be a multiple of 4");
     P2P_CHECK(!cfg.inline_check && cfg.diagnose == 0, "reduce: not with the inline check or the diagnosis");
   }
+  if (cfg.reduce_wire != WireFormat::Off) {
+    P2P_CHECK(cfg.reduce == ReduceType::Bf16 && cfg.wire == WireFormat::Off,
+              "reduce_wire: only with reduce bf16 (the format's payload is bf16), and not with wire");
+    P2P_CHECK(t.supports_reduce_wire(),
+              "reduce_wire: this transport cannot sum wire images (ipc with the kernel engine, or host)");
+    P2P_CHECK(cfg.bytes % kWireBlockBytes == 0, "reduce_wire: the message size must be a multiple of 64");
+    P2P_CHECK(!cfg.inline_check && cfg.diagnose == 0, "reduce_wire: not with the inline check or the diagnosis");
+    for (const RankOps& r : phase.ranks)
+      P2P_CHECK(r.recv_from.size() < static_cast<size_t>(kMaxWireReduceSrcs),
+                strfmt("reduce_wire: a rank of this phase has %zu incoming messages; one sum takes at most 8 operands "
+                       "(its own image and 7 incoming)", r.recv_from.size()));
+  }
   if (cfg.wire != WireFormat::Off) {
     P2P_CHECK(t.supports_wire(), "wire: this transport cannot unpack a wire image (ipc with the kernel engine, or host)");
     P2P_CHECK(cfg.bytes % kWireBlockBytes == 0, "wire: the message size must be a multiple of 64");
@@ -635,7 +657,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   const double hooked0 = now_seconds();
   if (cfg.before_timing) cfg.before_timing();
   if (active) {
-    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire);
+    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire);
     t.sync();
   }
   if (cfg.verify && cfg.warmup > 0) {
@@ -679,7 +701,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   auto post = [&](int i) {
     if (skip_some) t.set_discard(i % 2 == 0);
     const InlineRecords rec{static_cast<size_t>(i) * nrecv, cfg.salt};
-    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire);
+    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire);
   };
 
   double my_seconds = 0;

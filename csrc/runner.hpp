@@ -87,6 +87,16 @@ struct RunConfig {
   // kept slot with its sender's stream packed and unpacked.  Off: nothing
   // changes.
   WireFormat wire = WireFormat::Off;
+  // Receive-and-reduce of wire images (--reduce-wire; transport.hpp
+  // reduce_unpacked_from), only with reduce = Bf16: every operand of a
+  // receiver's sum is the MXFP8 / MXFP4 image of a bf16 operand stream.  The
+  // send region of every rank that sends or receives holds its image (the
+  // receiver's own one is operand 0), sends move wire_bytes, and a rank with
+  // receives posts one reduce_unpacked_from per iteration into receive slot 0
+  // of the generation.  At most kMaxWireReduceSrcs - 1 incoming messages per
+  // rank.  Timed, reported and checked as `reduce` (rates in payload bytes).
+  // Off: nothing changes.
+  WireFormat reduce_wire = WireFormat::Off;
   // Hooks around what a phase measures (--load brackets it with a background
   // load): run_phase calls them on every rank of a non-idle phase, in both
   // timings.  before_timing: after the payload and the poison are posted,
@@ -239,9 +249,11 @@ struct InlineRecords {
 // With `wire`, sends move the packed image and the receives are posted as
 // Transport::recv_unpacked.  With `reduce`, the receives are posted as one Transport::reduce_from into
 // slot gen * phase.max_recv_slots(), the local operand being send region gen.
+// With `reduce_wire` (and reduce = bf16), sends move the packed image and that
+// one call is Transport::reduce_unpacked_from.
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0,
                           const InlineRecords* check = nullptr, ReduceType reduce = ReduceType::Off,
-                          WireFormat wire = WireFormat::Off);
+                          WireFormat wire = WireFormat::Off, WireFormat reduce_wire = WireFormat::Off);
 
 // Receive generations for verified runs of messages up to `max_bytes` with
 // `slots` receive slots per iteration and up to `iters` iterations: as many as

@@ -29,6 +29,7 @@
 #include "prng.hpp"
 #include "reduce_op.hpp"
 #include "wire_op.hpp"
+#include "wire_reduce_op.hpp"
 
 namespace p2p {
 
@@ -153,6 +154,27 @@ class Transport {
   virtual void recv_unpacked(void* /*dst*/, size_t /*payload_bytes*/, int /*peer*/, size_t /*src_offset*/,
                              WireFormat /*fmt*/) {}
   virtual VerifyResult verify_unpacked(const void* /*p*/, size_t /*payload_bytes*/, uint64_t /*seed*/, WireFormat /*fmt*/) {
+    return {};
+  }
+
+  // ---- receive-and-reduce of wire images (--reduce-wire; wire_reduce_op.hpp) ----
+  // reduce_from whose every operand is an MXFP8 / MXFP4 wire image: dst (a
+  // registered receive slot) receives payload_bytes of bf16, the f32 sum of
+  // `local_image` (the receiver's own send region, operand 0) and the image at
+  // `src_offset` of the send buffer of every peer in `peers`, in that order,
+  // rounded once.  Posted inside a group, once per group at most; the matching
+  // sends move wire_bytes(payload_bytes).  The IPC pull engine does it in one
+  // launch of the gfx950 wire-reduce kernel (at most kMaxWireReduceSrcs
+  // operands), the host transport receives the images into scratch and sums
+  // on the CPU.  Send regions are filled with fill_packed.
+  //   verify_reduced_unpacked  blocking: p against the sum of the operand
+  //                            streams `seeds` (operand order), each packed
+  //                            and unpacked; a wrong 32-bit word counted once.
+  virtual bool supports_reduce_wire() const { return false; }
+  virtual void reduce_unpacked_from(void* /*dst*/, size_t /*payload_bytes*/, const void* /*local_image*/,
+                                    const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/) {}
+  virtual VerifyResult verify_reduced_unpacked(const void* /*p*/, size_t /*payload_bytes*/,
+                                               const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/) {
     return {};
   }
 

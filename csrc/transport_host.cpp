@@ -188,6 +188,54 @@ VerifyResult host_verify_unpacked(const void* p, size_t n, uint64_t seed, WireFo
   return r;
 }
 
+// ---- sum of wire images (wire_reduce_op.hpp) ----
+void host_wire_reduce(void* out, const void* const* images, int k, size_t n, WireFormat f) {
+  check_wire(n, f, "host_wire_reduce");
+  P2P_CHECK(k >= 1 && k <= kMaxWireReduceSrcs, "host_wire_reduce: 1..8 images");
+  for_each_wire_block(n, f, [&](size_t at, size_t elems, size_t scale) {
+    uint32_t w[kMaxWireReduceSrcs][16];
+    for (int j = 0; j < k; ++j) {
+      const auto* in = static_cast<const uint8_t*>(images[j]);
+      uint16_t x[kWireBlockElems];
+      wire_unpack_block(in + elems, in[scale], x, f);
+      for (uint32_t i = 0; i < 16; ++i) w[j][i] = x[2 * i] | static_cast<uint32_t>(x[2 * i + 1]) << 16;
+    }
+    for (uint32_t i = 0; i < 16; ++i) {
+      uint32_t col[kMaxWireReduceSrcs];
+      for (int j = 0; j < k; ++j) col[j] = w[j][i];
+      const uint32_t r = reduce_word(col, k, ReduceType::Bf16);
+      std::memcpy(static_cast<char*>(out) + at + 4 * i, &r, 4);
+    }
+  });
+}
+
+VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f) {
+  check_wire(n, f, "host_verify_wire_reduced");
+  P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "host_verify_wire_reduced: 1..8 operand seeds");
+  VerifyResult r;
+  for (size_t at = 0; at < n; at += kWireBlockBytes) {
+    uint16_t x[kMaxWireReduceSrcs][kWireBlockElems];
+    uint32_t sb[kMaxWireReduceSrcs];
+    for (int j = 0; j < nseeds; ++j) {
+      wire_operand_block(seeds[j], at / kWireBlockBytes, x[j]);
+      uint32_t amax = 0;
+      for (uint32_t i = 0; i < kWireBlockElems; ++i) amax = std::max<uint32_t>(amax, x[j][i] & 0x7FFFu);
+      sb[j] = wire_scale_byte(amax, f);
+    }
+    for (uint32_t i = 0; i < 16; ++i) {
+      uint32_t w[kMaxWireReduceSrcs], got;
+      for (int j = 0; j < nseeds; ++j) w[j] = x[j][2 * i] | static_cast<uint32_t>(x[j][2 * i + 1]) << 16;
+      std::memcpy(&got, static_cast<const char*>(p) + at + 4 * i, 4);
+      r.checksum += got;
+      if (got != wire_reduce_word(w, sb, nseeds, f)) {
+        if (!r.mismatches) r.first_bad = at + 4 * i;
+        ++r.mismatches;
+      }
+    }
+  }
+  return r;
+}
+
 namespace {
 
 void sockopts(int fd) {
@@ -322,11 +370,32 @@ class HostTransport final : public Transport {
     ops_.push_back({false, peer, unpacks_.back().wire.data(), unpacks_.back().wire.size()});
   }
 
+  // ---- sum of wire images: each image into scratch, then the CPU sum ----
+  bool supports_reduce_wire() const override { return true; }
+  VerifyResult verify_reduced_unpacked(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
+                                       WireFormat fmt) override {
+    return host_verify_wire_reduced(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt);
+  }
+  void reduce_unpacked_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers, size_t,
+                            WireFormat fmt) override {
+    P2P_CHECK(in_group_ && !wire_reduce_.dst, "host transport: one reduce_unpacked_from per group, inside the group");
+    P2P_CHECK(peers.size() < static_cast<size_t>(kMaxWireReduceSrcs),
+              "host transport: a sum of wire images has at most 8 operands (the own one and 7 incoming)");
+    const size_t image = wire_bytes(payload_bytes, fmt);
+    wire_reduce_ = {dst, payload_bytes, local_image, fmt, peers.size()};
+    if (scratch_.size() < image * peers.size()) scratch_.resize(image * peers.size());
+    for (size_t i = 0; i < peers.size(); ++i) {
+      P2P_CHECK(peers[i] >= 0 && peers[i] < n_, "bad peer");
+      ops_.push_back({false, peers[i], scratch_.data() + i * image, image});
+    }
+  }
+
   void group_begin() override {
     P2P_CHECK(!in_group_, "nested group");
     in_group_ = true;
     ops_.clear();
     reduce_ = {};
+    wire_reduce_ = {};
     unpacks_.clear();
   }
   void send(const void* p, size_t bytes, int peer) override {
@@ -355,6 +424,13 @@ class HostTransport final : public Transport {
       host_reduce(reduce_.dst, operands.data(), static_cast<int>(operands.size()), reduce_.bytes, reduce_.dtype);
     }
     reduce_ = {};
+    if (wire_reduce_.dst && !discarding()) {
+      const size_t image = wire_bytes(wire_reduce_.bytes, wire_reduce_.fmt);
+      std::vector<const void*> images{wire_reduce_.local_image};
+      for (size_t i = 0; i < wire_reduce_.npeers; ++i) images.push_back(scratch_.data() + i * image);
+      host_wire_reduce(wire_reduce_.dst, images.data(), static_cast<int>(images.size()), wire_reduce_.bytes, wire_reduce_.fmt);
+    }
+    wire_reduce_ = {};
     // Injected skip fault: the images were read off the wire and are dropped.
     for (const PendingUnpack& u : unpacks_)
       if (!discarding()) host_wire_unpack(u.dst, u.wire.data(), u.bytes, u.fmt);
@@ -375,6 +451,13 @@ class HostTransport final : public Transport {
     size_t bytes = 0;
     const void* local_src = nullptr;
     ReduceType dtype = ReduceType::Off;
+    size_t npeers = 0;
+  };
+  struct PendingWireReduce {
+    void* dst = nullptr;
+    size_t bytes = 0;  // payload
+    const void* local_image = nullptr;
+    WireFormat fmt = WireFormat::Off;
     size_t npeers = 0;
   };
   struct PendingUnpack {
@@ -485,6 +568,7 @@ class HostTransport final : public Transport {
   std::vector<int> fds_;
   bool in_group_ = false;
   std::vector<Op> ops_;
+  PendingWireReduce wire_reduce_;  // the open group's reduce_unpacked_from, summed in group_end()
   PendingReduce reduce_;       // the open group's reduce_from, summed in group_end()
   std::vector<char> scratch_;  // its incoming messages, one after the other
   std::vector<PendingUnpack> unpacks_;  // the open group's recv_unpacked, widened in group_end()

@@ -195,6 +195,7 @@ class IpcTransport final : public GpuTransport {
     ops_.clear();
     checked_ops_.clear();
     reduce_ = {};
+    wire_reduce_ = {};
     unpack_ops_.clear();
     if (plan_) plan_->group_begin();
   }
@@ -311,6 +312,35 @@ class IpcTransport final : public GpuTransport {
     op.payload_bytes = payload_bytes;
     op.coherent = peer != rank_;
     unpack_ops_.push_back(op);
+  }
+
+  // ---- sum of wire images (transport.hpp): the pull engine's wire-reduce
+  // kernel loads the own image and every peer's and stores their bf16 sum,
+  // one launch per group (kernels.hpp launch_wire_reduce).
+  bool supports_reduce_wire() const override { return engine_ == "kernel"; }
+  void reduce_unpacked_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
+                            size_t src_offset, WireFormat fmt) override {
+    P2P_CHECK(supports_reduce_wire(), "ipc transport: --reduce-wire needs --ipc-engine kernel");
+    P2P_CHECK(in_group_ && !wire_reduce_.dst, "ipc transport: one reduce_unpacked_from per group, inside the group");
+    P2P_CHECK(peers.size() < static_cast<size_t>(kMaxWireReduceSrcs),
+              "ipc transport: the wire-reduce kernel sums at most 8 images (the own one and 7 incoming)");
+    const Registration* reg = nullptr;
+    for (const auto& r : regs_)
+      if (slot_of(r, dst) >= 0 && payload_bytes <= r.slot_bytes) reg = &r;
+    P2P_CHECK(reg, "ipc transport reduces only into a registered receive slot");
+    P2P_CHECK(src_offset + wire_bytes(payload_bytes, fmt) <= reg->send_bytes,
+              "ipc transport: wire image beyond the peer's send buffer");
+    if (discarding()) return;  // injected skip fault: the launch is not issued
+    wire_reduce_ = {};
+    wire_reduce_.dst = dst;
+    wire_reduce_.payload_bytes = payload_bytes;
+    wire_reduce_.src[wire_reduce_.nsrc++] = local_image;
+    for (int peer : peers) {
+      P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
+      if (peer != rank_) wire_reduce_.coherent_mask |= 1u << wire_reduce_.nsrc;
+      wire_reduce_.src[wire_reduce_.nsrc++] = static_cast<const char*>(reg->peer_send.ptr[static_cast<size_t>(peer)]) + src_offset;
+    }
+    wire_reduce_fmt_ = fmt;
   }
 
   void group_end() override {
@@ -466,6 +496,10 @@ class IpcTransport final : public GpuTransport {
       dev::launch_reduce_wide(reduce_.dst, reduce_.bytes, reduce_.srcs.data(), reduce_.coherent.data(),
                               static_cast<int>(reduce_.srcs.size()), false, reduce_.dtype, stream_, 0, partial_);
       reduce_ = {};
+    }
+    if (wire_reduce_.dst) {
+      dev::launch_wire_reduce(wire_reduce_, wire_reduce_fmt_, stream_);
+      wire_reduce_ = {};
     }
     if (!unpack_ops_.empty()) {
       dev::launch_multi_unpack(unpack_ops_.data(), static_cast<int>(unpack_ops_.size()), unpack_fmt_, stream_);
@@ -639,6 +673,9 @@ class IpcTransport final : public GpuTransport {
   // Pull kernel: the open group's recv_unpacked ops, launched in flush().
   std::vector<dev::UnpackOp> unpack_ops_;
   WireFormat unpack_fmt_ = WireFormat::Off;
+  // Pull kernel: the open group's reduce_unpacked_from, launched in flush().
+  dev::WireReduceOp wire_reduce_;
+  WireFormat wire_reduce_fmt_ = WireFormat::Off;
   void* partial_ = nullptr;  // f32 planes of a wide bf16 sum (kernels.hpp reduce_partial_bytes)
   size_t partial_bytes_ = 0;
 

@@ -1,0 +1,64 @@
+// Receive-and-reduce of block-scaled operands (--reduce-wire): every operand of
+// a receiver's sum is an MXFP8 / MXFP4 wire image (wire_op.hpp: format, tiles,
+// scale rule), the sum leaves as bf16.  Shared by the gfx950 kernels
+// (wire_reduce.hip), the host transport and the host-side regeneration of
+// expected values, so all of them produce the same bits.  Nothing new is
+// computed here: the function below composes wire_op.hpp and reduce_op.hpp.
+//
+// Arithmetic.  An element is dequantised to f32 (exactly a bf16 value: a 4- or
+// 2-bit significand times a power of two), the K operands are added in operand
+// order (operand 0 is the receiver's own image, then the incoming ones as
+// posted) in a chain of plain f32 adds, and the sum is rounded once, to
+// nearest even, to bf16.  That is reduce_word with ReduceType::Bf16 over the
+// widened words.
+//
+// Range.  Operand exponent fields lie in [64, 110] (wire_operand_word), so a
+// block's scale byte is >= 64 - 8 = 56 (mxfp8) or >= 64 - 2 = 62 (mxfp4) and
+// <= 110 - 1.  The smallest non-zero dequantised magnitude is e4m3's smallest
+// subnormal under the smallest scale, 2^-9 x 2^(56 - 127) = 2^-80 (mxfp4:
+// 0.5 x 2^(62 - 127) = 2^-66); every operand and every partial sum is a
+// multiple of it, so a non-zero partial sum is at least 2^-80, far above f32's
+// subnormal range (< 2^-126).  The largest operand is below 2^9 x 2^(109 - 127)
+// = 2^-9, and kMaxWireReduceSrcs = 8 of them stay below 2^-6: nothing
+// overflows.  No add produces or consumes a subnormal, so the device's
+// denormal mode cannot change a bit, and the single bf16 rounding sees a
+// normal f32 or a zero.
+//
+// Zeros are real operands here, unlike in reduce_op.hpp: the codes 0x00 / 0x80
+// (mxfp8) and 0x0 / 0x8 (mxfp4) occur, and the sign of a zero is kept by the
+// dequantisation.  Signed zeros follow IEEE addition in round-to-nearest:
+// (+0) + (-0) = +0, (-0) + (-0) = -0, and an exact cancellation x + (-x) gives
+// +0.  A single operand passes through with its sign.  reduce_pack_bf16 keeps
+// the sign of a zero on both sides: v_cvt_pk_bf16_f32 maps +-0 to +-0, and the
+// host's integer form adds 0x7FFF to 0x00000000 / 0x80000000, which carries
+// nothing into the upper half, so 0x0000 / 0x8000 come out.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "reduce_op.hpp"
+#include "wire_op.hpp"
+
+namespace p2p {
+
+constexpr int kMaxWireReduceSrcs = 8;  // operands of one sum: the own image and up to 7 incoming
+
+// One 32-bit word (two elements) of the sum.  w[k] is operand k's word of its
+// operand stream (wire_operand_word), sb[k] the scale byte of the block that
+// word lies in; k in 1..kMaxWireReduceSrcs.
+P2P_HD uint32_t wire_reduce_word(const uint32_t* w, const uint32_t* sb, int k, WireFormat f) {
+  ReduceAcc a = reduce_begin(wire_roundtrip_word(w[0], sb[0], f), ReduceType::Bf16);
+  for (int i = 1; i < k; ++i) reduce_add(a, wire_roundtrip_word(w[i], sb[i], f), ReduceType::Bf16);
+  return reduce_finish(a, ReduceType::Bf16);
+}
+
+// Host side (transport_host.cpp).  n is the payload size, a multiple of 64.
+// out: n bytes of bf16 = the sum of the k wire images (wire_bytes(n, f) each)
+// in order.  Any alignment.
+void host_wire_reduce(void* out, const void* const* images, int k, size_t n, WireFormat f);
+// Compares p with the sum of the operand streams `seeds` (operand order), each
+// packed and unpacked by the shared functions; a wrong 32-bit word counts once.
+VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f);
+
+}  // namespace p2p

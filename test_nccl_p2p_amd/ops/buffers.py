@@ -361,6 +361,33 @@ def reference_wire_roundtrip(words: torch.Tensor, fmt: str) -> torch.Tensor:
     return torch.stack([bits & 0xFF, bits >> 8], dim=1).to(torch.uint8).reshape(-1)
 
 
+def wire_reduce_(dst: torch.Tensor, srcs, fmt: str, *, coherent: bool = False, max_blocks: int = 0,
+                 lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """The bytes of ``dst`` as bf16 = the sum of the 1..8 'mxfp8' / 'mxfp4'
+    wire images ``srcs`` in that order, dequantised and added in float32 and
+    rounded once, with the gfx950 wire-reduce kernel (the IPC pull engine's
+    receive under ``--reduce-wire``; stream-ordered)."""
+    nbytes = _check_tensor(dst)
+    nat = require_native()
+    if any(_check_tensor(s) < nat.wire_bytes(nbytes, fmt) for s in srcs):
+        raise ValueError("wire_reduce_: a source holds less than wire_bytes() of dst")
+    nat.wire_reduce(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, fmt, _stream(stream), coherent, max_blocks, lanes)
+    return dst
+
+
+def reference_wire_reduce(operands, fmt: str) -> torch.Tensor:
+    """What :func:`wire_reduce_` leaves (uint8, bf16 payload bytes) for the
+    images of ``operands`` (int64 bf16 word tensors, in order):
+    :func:`reference_wire_roundtrip` of each (float64 quantisation) fed to
+    :func:`reference_reduce` as bf16 (a ``torch.float32`` add chain on the CPU
+    and one ``.to(torch.bfloat16)``)."""
+    widened = []
+    for w in operands:
+        b = reference_wire_roundtrip(w, fmt).to(torch.int64).reshape(-1, 4)
+        widened.append(b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16) | (b[:, 3] << 24))
+    return words_to_bytes(reference_reduce(widened, "bf16"))
+
+
 # ---------------------------------------------------------------- diagnosis --
 
 class GranuleRecord(NamedTuple):
