@@ -150,6 +150,14 @@ data
                          timed and reported in payload bytes, the sum is checked bit for bit.
                          --transport ipc --ipc-engine kernel, or host; sizes multiples of 64;
                          not with --wire, --verify-inline, --diagnose, --reference or --resume
+      --reduce-out FORMAT  bf16 (default) | wire, with --reduce bf16 --reduce-wire F: what the sum
+                         leaves.  wire: the middle hop of a quantised ring or combine.  One
+                         launch of the gfx950 wire-reduce-pack kernel sums the images, rounds
+                         the sum once to bf16, requantises it under each block's no-clip scale
+                         and stores a wire image in format F, ready to forward: bit for bit what
+                         --reduce-out bf16 followed by a pack would give, without the bf16
+                         round trip through memory.  Flows stay in payload bytes; the image is
+                         checked bit for bit.  Same transports and exclusions as --reduce-wire
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -301,7 +309,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
                                     "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load", "--stream-sizes",
-                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire", "--reduce-wire"};
+                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire", "--reduce-wire", "--reduce-out"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -420,6 +428,14 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
         *exit_code = 1;
         return false;
       }
+    } else if (a == "--reduce-out") {
+      const std::string v = next();
+      if (v != "bf16" && v != "wire") {
+        std::fprintf(stderr, "p2p_matrix: --reduce-out '%s': bf16 or wire\n", v.c_str());
+        *exit_code = 1;
+        return false;
+      }
+      cfg->run.reduce_out = v == "wire" ? ReduceOut::Wire : ReduceOut::Bf16;
     } else if (a == "--load") {
       const std::string v = next();
       std::string why;
@@ -556,6 +572,31 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     }
     if (!why.empty()) {
       std::fprintf(stderr, "p2p_matrix: --load cannot be combined with %s: %s\n", with.c_str(), why.c_str());
+      *exit_code = 1;
+      return false;
+    }
+  }
+  // --reduce-out wire: the requantised output of a --reduce-wire sum, so it
+  // runs where that option runs and beside what it runs beside.  Checked
+  // first: its refusals name this option.
+  if (cfg->run.reduce_out == ReduceOut::Wire) {
+    std::string why;
+    if (cfg->run.reduce != ReduceType::Bf16 || cfg->run.reduce_wire == WireFormat::Off)
+      why = "needs --reduce bf16 --reduce-wire FORMAT: the image it stores is the requantised sum of wire images, in their format";
+    if (why.empty() && !(cfg->transport == "host" || (cfg->transport == "ipc" && cfg->ipc_engine == "kernel")))
+      why = strfmt("needs --transport ipc --ipc-engine kernel (the gfx950 wire-reduce-pack kernel) or --transport host; %s%s%s "
+                   "sums no wire images", cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",
+                   cfg->transport == "ipc" ? cfg->ipc_engine.c_str() : "");
+    if (why.empty() && cfg->run.inline_check)
+      why = "cannot be combined with --verify-inline: that check compares a copied message with the raw stream";
+    if (why.empty() && cfg->run.diagnose > 0)
+      why = "cannot be combined with --diagnose: the diagnosis explains a slot by one sender's raw streams";
+    if (why.empty() && cfg->reference_buffers)  // set by --reference alone
+      why = "cannot be combined with --reference: that is the reference's run, which only moves its payload";
+    if (why.empty() && cfg->resume)
+      why = "cannot be combined with --resume: the runs in the file are counted by mode, direction and size alone";
+    if (!why.empty()) {
+      std::fprintf(stderr, "p2p_matrix: --reduce-out wire %s\n", why.c_str());
       *exit_code = 1;
       return false;
     }

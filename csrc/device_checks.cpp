@@ -98,6 +98,16 @@ VerifyResult DeviceChecks::verify_wire_reduced(const void* p, size_t payload_byt
   return verify_result();
 }
 
+VerifyResult DeviceChecks::verify_wire_reduced_packed(const void* image, size_t payload_bytes, const std::vector<uint64_t>& seeds,
+                                                      WireFormat fmt, hipStream_t stream, const StreamWait& wait) {
+  acc_.reserve(dev::kVerifyShards, [] {});
+  dev::launch_verify_reset(acc_.device(), stream);
+  dev::launch_verify_wire_reduced_packed(image, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, acc_.device(), stream);
+  acc_.readback(1, stream);
+  wait();
+  return verify_result();
+}
+
 std::vector<VerifyResult> DeviceChecks::verify_many(const std::vector<VerifyJob>& jobs, hipStream_t stream,
                                                     const StreamWait& wait) {
   if (jobs.empty()) return {};

@@ -91,6 +91,10 @@ class DeviceChecks {
   VerifyResult verify_wire_reduced(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds, WireFormat fmt,
                                    hipStream_t stream, const StreamWait& wait);
 
+  // The requantised sum (Transport::verify_reduced_packed; kernels.hpp launch_verify_wire_reduced_packed).
+  VerifyResult verify_wire_reduced_packed(const void* image, size_t payload_bytes, const std::vector<uint64_t>& seeds,
+                                          WireFormat fmt, hipStream_t stream, const StreamWait& wait);
+
   // ---- batched verify (Transport::verify_many) ----
   // One buffer at a time under --verify-impl stride or P2P_VERIFY_BATCH=0.
   std::vector<VerifyResult> verify_many(const std::vector<VerifyJob>& jobs, hipStream_t stream, const StreamWait& wait);

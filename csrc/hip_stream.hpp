@@ -96,6 +96,12 @@ class GpuTransport : public Transport {
     return checks_.verify_wire_reduced(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); });
   }
 
+  VerifyResult verify_reduced_packed(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
+                                     WireFormat fmt) override {
+    before_buffer_work();
+    return checks_.verify_wire_reduced_packed(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); });
+  }
+
   int mark() override;  // one event per mark on the main stream
   double elapsed_ms(int from, int to) override;
   void clear_marks() override { next_event_ = 0; }

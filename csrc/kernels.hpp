@@ -33,6 +33,9 @@
 //   wsum    — receive-and-reduce of wire images (--reduce-wire, wire_reduce.hip):
 //             K MXFP8 / MXFP4 images summed in f32 into bf16 in one launch,
 //             and the check of such a sum
+//   wpack   — the same sum requantised (--reduce-out wire, wire_reduce_pack.hip):
+//             K images in, one image of their bf16 sum out, in one launch,
+//             and the check of such an image
 //
 // Measured on MI355X (profiles/, scripts/fill_probe.hip): streaming at one
 // 16 B access per lane with one block per 4 KiB (a "full grid", up to 2^20
@@ -283,6 +286,32 @@ void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stre
 // launch_verify's (reset acc first).  Never inside timing.
 void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint64_t* seeds, int nseeds, WireFormat fmt,
                                 VerifyAccum* acc, hipStream_t stream);
+
+// ---- the same hop with a requantised output (wire_reduce_pack.hip; --reduce-out wire) ----
+// launch_wire_reduce whose op.dst receives wire_bytes(payload_bytes, fmt)
+// bytes: the wire image, in the operands' format, of the bf16 sum (wire_op.hpp
+// wire_pack_block of wire_reduce_op.hpp's sum: the f32 chain is rounded once
+// to bf16, and that value is quantised under the no-clip scale of the block's
+// bf16 amax), padding zeroed, bit-identical to launch_wire_reduce into scratch
+// followed by launch_pack.  Load side and lane mappings as launch_wire_reduce;
+// the epilogue rounds the 16 accumulators to bf16, completes the block's amax
+// over its 4 (split) or 2 (contiguous) lanes with xor shuffles, narrows with
+// the scaled conversions and stores the codes with 16 B / 8 B (contiguous) or
+// two 8 B / 4 B (split) non-temporal stores; the tile's 128 scale bytes and
+// their padding leave as 16 B stores through a double-buffered LDS stage, one
+// barrier per tile.  Same argument rules as launch_wire_reduce; dst is local.
+// Auto is contiguous here, the mapping measured faster in every cell.
+void launch_wire_reduce_packed(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks = 0,
+                               WireLanes lanes = WireLanes::Auto);
+// The check of such an image, in launch_verify_wire_reduced's geometry (one
+// payload vector per lane, 4 lanes per block): regenerates and sums the
+// operand streams, takes the block's amax of the sums, quantises with the
+// integer functions and compares the image's code words and scale byte.  A
+// wrong 32-bit word of codes counts once, a wrong scale byte once; first_bad is
+// the lowest byte offset in the image of either; the checksum sums the code
+// words and the scale bytes; the padding is not read.
+void launch_verify_wire_reduced_packed(const void* image, size_t payload_bytes, const uint64_t* seeds, int nseeds,
+                                       WireFormat fmt, VerifyAccum* acc, hipStream_t stream);
 
 // ---- device-initiated ping-pong (pingpong.hip) ----
 // One wave per role.  The leader writes message i (payload words = base+i+1,

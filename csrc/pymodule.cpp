@@ -113,7 +113,7 @@ class Session {
   std::string run(const std::string& mode, const std::string& dir, size_t bytes, int iters, int warmup,
                   const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
                   int diagnose, bool inline_check, const std::string& load, const std::string& reduce,
-                  const std::string& wire, const std::string& reduce_wire) {
+                  const std::string& wire, const std::string& reduce_wire, const std::string& reduce_out) {
     LoadSpec load_spec;
     std::string why;
     P2P_CHECK(load.empty() || parse_load_spec(load, &load_spec, &why), "load '" + load + "': " + why);
@@ -150,6 +150,12 @@ class Session {
                   (cfg.reduce == ReduceType::Bf16 && wire.empty() && t_->supports_reduce_wire() && bytes % kWireBlockBytes == 0),
               "reduce_wire needs reduce='bf16' (the format's payload is bf16), no wire, transport 'ipc' / 'ipc:kernel' or "
               "'host', and bytes a multiple of 64");
+    // reduce_out="wire": the sum leaves as a wire image in reduce_wire's format (RunConfig::reduce_out).
+    P2P_CHECK(reduce_out.empty() || reduce_out == "bf16" || reduce_out == "wire", "reduce_out '" + reduce_out + "': bf16 or wire");
+    P2P_CHECK(reduce_out != "wire" || (cfg.reduce_wire != WireFormat::Off && !inline_check && diagnose <= 0),
+              "reduce_out='wire' needs reduce='bf16' and reduce_wire (the image's format is the operands'), and neither "
+              "inline_check nor diagnose");
+    if (reduce_out == "wire") cfg.reduce_out = ReduceOut::Wire;
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
@@ -531,6 +537,34 @@ py::tuple device_verify_wire_reduced(uintptr_t ptr, size_t payload_bytes, const 
   {
     py::gil_scoped_release nogil;
     r = c.verify_wire_reduced(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st));
+  }
+  return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
+}
+
+// ---- the same sum, requantised (kernels.hpp launch_wire_reduce_packed) ----
+void device_wire_reduce_packed(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t payload_bytes, const std::string& fmt,
+                               uintptr_t stream, bool coherent, int max_blocks, const std::string& lanes) {
+  const WireFormat f = wire_format_arg(fmt);
+  if (srcs.empty() || srcs.size() > static_cast<size_t>(kMaxWireReduceSrcs))
+    throw py::value_error("wire_reduce_packed: 1..8 source images");
+  dev::WireReduceOp op;
+  op.dst = reinterpret_cast<void*>(dst);
+  op.payload_bytes = wire_payload_arg(payload_bytes);
+  for (uintptr_t s : srcs) op.src[op.nsrc++] = reinterpret_cast<const void*>(s);
+  if (coherent) op.coherent_mask = (1u << op.nsrc) - 1u;
+  dev::launch_wire_reduce_packed(op, f, as_stream(stream), max_blocks, wire_lanes_arg(lanes));
+}
+
+py::tuple device_verify_wire_reduced_packed(uintptr_t ptr, size_t payload_bytes, const std::vector<uint64_t>& seeds,
+                                            const std::string& fmt, uintptr_t stream) {
+  const WireFormat f = wire_format_arg(fmt);
+  wire_payload_arg(payload_bytes);
+  DeviceChecks& c = checks_for_current_device();
+  hipStream_t st = as_stream(stream);
+  VerifyResult r;
+  {
+    py::gil_scoped_release nogil;
+    r = c.verify_wire_reduced_packed(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st));
   }
   return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
@@ -1030,7 +1064,7 @@ PYBIND11_MODULE(_p2pcore, m) {
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
            py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
            py::arg("inline_check") = false, py::arg("load") = "", py::arg("reduce") = "", py::arg("wire") = "",
-           py::arg("reduce_wire") = "", py::call_guard<NativeCall, py::gil_scoped_release>())
+           py::arg("reduce_wire") = "", py::arg("reduce_out") = "", py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("device_latency", &Session::device_latency, py::arg("bytes") = 8, py::arg("iters") = 1000,
@@ -1313,6 +1347,30 @@ PYBIND11_MODULE(_p2pcore, m) {
         return py::bytes(out);
       }, py::arg("images"), py::arg("payload_bytes"), py::arg("fmt"),
       "CPU sum of wire images in order as bf16 bytes, bit-compatible with the wire-reduce kernel.");
+  m.def("wire_reduce_packed", &device_wire_reduce_packed, py::arg("dst"), py::arg("srcs"), py::arg("payload_bytes"),
+        py::arg("fmt"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0, py::arg("lanes") = "auto",
+        "The gfx950 wire-reduce-pack kernel: dst = wire_bytes(payload_bytes, fmt) bytes, the wire image in fmt of the bf16 sum "
+        "wire_reduce gives for the 1..8 images at srcs, in one launch (coherent, lanes: as wire_reduce).");
+  m.def("verify_wire_reduced_packed", &device_verify_wire_reduced_packed, py::arg("ptr"), py::arg("payload_bytes"),
+        py::arg("seeds"), py::arg("fmt"), py::arg("stream") = 0,
+        "Compares the image with the packed sum of the operand streams `seeds`: (wrong 32-bit code words + wrong scale bytes, "
+        "checksum of code words and scale bytes, first bad byte offset in the image or 2**64-1).");
+  m.def("host_wire_reduce_packed", [](const std::vector<py::bytes>& images, size_t payload_bytes, const std::string& fmt) {
+        const WireFormat f = wire_format_arg(fmt);
+        if (images.empty() || images.size() > static_cast<size_t>(kMaxWireReduceSrcs))
+          throw py::value_error("host_wire_reduce_packed: 1..8 images");
+        std::vector<std::string> data(images.begin(), images.end());
+        std::vector<const void*> p;
+        for (const std::string& d : data) {
+          if (d.size() != wire_bytes(wire_payload_arg(payload_bytes), f))
+            throw py::value_error("host_wire_reduce_packed: wire_bytes() per image");
+          p.push_back(d.data());
+        }
+        std::string out(wire_bytes(payload_bytes, f), '\0');
+        host_wire_reduce_packed(&out[0], p.data(), static_cast<int>(p.size()), payload_bytes, f);
+        return py::bytes(out);
+      }, py::arg("images"), py::arg("payload_bytes"), py::arg("fmt"),
+      "CPU sum of wire images, packed again: the image the wire-reduce-pack kernel stores, bit for bit.");
   m.attr("MAX_SIGNALS") = dev::kMaxSignals;
   m.def("signal", [](const FlagList& posts, const FlagList& waits, uintptr_t status_ptr, uint64_t timeout_ticks,
                      bool release_first, uintptr_t stream, uintptr_t trap_flag) {

@@ -229,6 +229,7 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
   if (rec.cfg.wire != WireFormat::Off) head.insert(head.size() - 1, strfmt(" wire=%s", wire_format_name(rec.cfg.wire)));
   if (rec.cfg.reduce_wire != WireFormat::Off)
     head.insert(head.size() - 1, strfmt(" reduce-wire=%s", wire_format_name(rec.cfg.reduce_wire)));
+  if (rec.cfg.reduce_out == ReduceOut::Wire) head.insert(head.size() - 1, " reduce-out=wire");
   std::fprintf(out, "\n== %s ==\n", head.c_str());
   bool blank_diag = rec.mode != Mode::Self && n > 1;
   auto gbs = flow_matrix_gbs(rec, n);
@@ -278,6 +279,10 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
   else if (rec.cfg.reduce != ReduceType::Off)
     std::fprintf(out, "  reduce: %s, every receiver sums its own shard and its incoming messages in one launch\n",
                  reduce_type_name(rec.cfg.reduce));
+  if (rec.cfg.reduce_out == ReduceOut::Wire)
+    std::fprintf(out, "  reduce-out: the sum is requantised in the same launch and stored as a %llu-byte %s image\n",
+                 static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)),
+                 wire_format_name(rec.cfg.reduce_wire));
   if (rec.cfg.wire != WireFormat::Off)
     std::fprintf(out, "  wire: %s, %llu wire bytes per %llu-byte bf16 message; rates are payload bytes (bf16 delivered)\n",
                  wire_format_name(rec.cfg.wire), static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.wire)),
@@ -416,6 +421,9 @@ std::string run_to_json(const RunRecord& rec, int n) {
     if (rec.cfg.reduce_wire != WireFormat::Off)  // --reduce-wire: how the operands arrive
       o << ",\"wire\":{\"format\":\"" << wire_format_name(rec.cfg.reduce_wire) << "\",\"payload_bytes\":" << rec.cfg.bytes
         << ",\"wire_bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire) << "}";
+    if (rec.cfg.reduce_out == ReduceOut::Wire)  // --reduce-out wire: what the sum leaves in the slot
+      o << ",\"out\":{\"format\":\"" << wire_format_name(rec.cfg.reduce_wire)
+        << "\",\"bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire) << "}";
     o << "}";
   }
   if (rec.cfg.wire != WireFormat::Off)  // present only when the option is on

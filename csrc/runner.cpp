@@ -136,7 +136,8 @@ std::vector<Transport::GroupFlow> group_flow_list(const Phase& phase) {
 }  // namespace
 
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen,
-                          const InlineRecords* check, ReduceType reduce, WireFormat wire, WireFormat reduce_wire) {
+                          const InlineRecords* check, ReduceType reduce, WireFormat wire, WireFormat reduce_wire,
+                          ReduceOut reduce_out) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const std::vector<int> rs = remote_slots(phase, t.rank());
   const int base = gen * std::max(1, phase.max_recv_slots());
@@ -154,7 +155,9 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
   const WireFormat image = wire != WireFormat::Off ? wire : reduce_wire;
   const size_t sent = image == WireFormat::Off ? bytes : static_cast<size_t>(wire_bytes(bytes, image));
   for (size_t j = 0; j < ops.send_to.size(); ++j) t.send_to_slot(bufs.send_at(off), sent, ops.send_to[j], base + rs[j]);
-  if (reduce_wire != WireFormat::Off && !ops.recv_from.empty())
+  if (reduce_wire != WireFormat::Off && reduce_out == ReduceOut::Wire && !ops.recv_from.empty())
+    t.reduce_packed_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce_wire);
+  else if (reduce_wire != WireFormat::Off && !ops.recv_from.empty())
     t.reduce_unpacked_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce_wire);
   else if (reduce != ReduceType::Off && !ops.recv_from.empty())
     t.reduce_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce);
@@ -264,7 +267,9 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
     for (int g = 0; g < gens && !ops.recv_from.empty(); ++g) {
       std::vector<uint64_t> seeds{generation_seed(t.rank(), cfg.bytes, cfg.salt, g)};
       for (int peer : ops.recv_from) seeds.push_back(generation_seed(peer, cfg.bytes, cfg.salt, g));
-      const VerifyResult v = cfg.reduce_wire != WireFormat::Off
+      const VerifyResult v = cfg.reduce_out == ReduceOut::Wire
+                                 ? t.verify_reduced_packed(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire)
+                                 : cfg.reduce_wire != WireFormat::Off
                                  ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire)
                                  : t.verify_reduced(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce);
       bad += v.mismatches;
@@ -442,7 +447,7 @@ void rechunk_until_warmup_verifies(Transport& t, Bootstrap& boot, const Phase& p
     }
     boot.barrier();
     if (active) {
-      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire);
+      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out);
       t.sync();
     }
     bad = boot.allreduce_sum_u64(local_mismatches());
@@ -630,6 +635,8 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
                 strfmt("reduce_wire: a rank of this phase has %zu incoming messages; one sum takes at most 8 operands "
                        "(its own image and 7 incoming)", r.recv_from.size()));
   }
+  P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Off,
+            "reduce_out wire: only with reduce_wire (the image's format is the operands')");
   if (cfg.wire != WireFormat::Off) {
     P2P_CHECK(t.supports_wire(), "wire: this transport cannot unpack a wire image (ipc with the kernel engine, or host)");
     P2P_CHECK(cfg.bytes % kWireBlockBytes == 0, "wire: the message size must be a multiple of 64");
@@ -657,7 +664,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   const double hooked0 = now_seconds();
   if (cfg.before_timing) cfg.before_timing();
   if (active) {
-    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire);
+    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out);
     t.sync();
   }
   if (cfg.verify && cfg.warmup > 0) {
@@ -701,7 +708,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   auto post = [&](int i) {
     if (skip_some) t.set_discard(i % 2 == 0);
     const InlineRecords rec{static_cast<size_t>(i) * nrecv, cfg.salt};
-    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire);
+    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out);
   };
 
   double my_seconds = 0;

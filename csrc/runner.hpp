@@ -33,6 +33,8 @@ enum class Timing { Events, Wallclock };
 const char* timing_name(Timing t);
 Timing parse_timing(const std::string& s);
 
+enum class ReduceOut : int { Bf16 = 0, Wire = 1 };
+
 struct RunConfig {
   size_t bytes = 32u << 20;  // reference: msg_size = 32 MiB (p2p_matrix.cc:124)
   int iters = 128;           // reference: count = 128 (p2p_matrix.cc:132)
@@ -97,6 +99,13 @@ struct RunConfig {
   // rank.  Timed, reported and checked as `reduce` (rates in payload bytes).
   // Off: nothing changes.
   WireFormat reduce_wire = WireFormat::Off;
+  // What a reduce_wire sum leaves in the receive slot (--reduce-out).  Bf16:
+  // bytes of bf16, as above.  Wire: the sum requantised, wire_bytes(bytes) of
+  // an image in the operands' format that the next hop of a quantised ring
+  // could forward (transport.hpp reduce_packed_from), checked against the
+  // packed sum of the operand streams.  Flows are still timed and reported in
+  // payload bytes.  Wire needs reduce_wire.
+  ReduceOut reduce_out = ReduceOut::Bf16;
   // Hooks around what a phase measures (--load brackets it with a background
   // load): run_phase calls them on every rank of a non-idle phase, in both
   // timings.  before_timing: after the payload and the poison are posted,
@@ -250,10 +259,12 @@ struct InlineRecords {
 // Transport::recv_unpacked.  With `reduce`, the receives are posted as one Transport::reduce_from into
 // slot gen * phase.max_recv_slots(), the local operand being send region gen.
 // With `reduce_wire` (and reduce = bf16), sends move the packed image and that
-// one call is Transport::reduce_unpacked_from.
+// one call is Transport::reduce_unpacked_from, or reduce_packed_from with
+// `reduce_out` = Wire.
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0,
                           const InlineRecords* check = nullptr, ReduceType reduce = ReduceType::Off,
-                          WireFormat wire = WireFormat::Off, WireFormat reduce_wire = WireFormat::Off);
+                          WireFormat wire = WireFormat::Off, WireFormat reduce_wire = WireFormat::Off,
+                          ReduceOut reduce_out = ReduceOut::Bf16);
 
 // Receive generations for verified runs of messages up to `max_bytes` with
 // `slots` receive slots per iteration and up to `iters` iterations: as many as

@@ -177,6 +177,20 @@ class Transport {
                                                const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/) {
     return {};
   }
+  // The same hop with a requantised output (--reduce-out wire): dst receives
+  // wire_bytes(payload_bytes) bytes, the wire image in `fmt` of that bf16 sum
+  // (wire_reduce_op.hpp), ready to be forwarded.  Same posting rules, same
+  // transports; the IPC pull engine still needs one launch (the gfx950
+  // wire-reduce-pack kernel), the host transport sums and packs on the CPU.
+  //   verify_reduced_packed  blocking: the image at p against the packed sum
+  //                          of the operand streams; a wrong 32-bit word of
+  //                          element codes and a wrong scale byte count once.
+  virtual void reduce_packed_from(void* /*dst*/, size_t /*payload_bytes*/, const void* /*local_image*/,
+                                  const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/) {}
+  virtual VerifyResult verify_reduced_packed(const void* /*p*/, size_t /*payload_bytes*/,
+                                             const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/) {
+    return {};
+  }
 
   // Multi-path transports (IPC relay engine) move parts of a message through
   // ranks that are neither its sender nor its receiver, so every rank must

@@ -236,6 +236,52 @@ VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* s
   return r;
 }
 
+// ---- the same sum, requantised (wire_reduce_op.hpp) ----
+void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f) {
+  check_wire(n, f, "host_wire_reduce_packed");
+  std::vector<char> sum(n);
+  host_wire_reduce(sum.data(), images, k, n, f);
+  host_wire_pack(out_image, sum.data(), n, f);
+}
+
+VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f) {
+  check_wire(n, f, "host_verify_wire_reduced_packed");
+  P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "host_verify_wire_reduced_packed: 1..8 operand seeds");
+  const auto* in = static_cast<const uint8_t*>(image);
+  const uint32_t code_words = wire_block_elem_bytes(f) / 4, per = 16 / code_words;  // sum words per word of codes
+  VerifyResult r;
+  auto wrong = [&](size_t at) {
+    r.first_bad = std::min<uint64_t>(r.first_bad, at);
+    ++r.mismatches;
+  };
+  for_each_wire_block(n, f, [&](size_t at, size_t elems, size_t scale) {
+    uint16_t x[kMaxWireReduceSrcs][kWireBlockElems];
+    uint32_t sb[kMaxWireReduceSrcs], sum[16], amax = 0;
+    for (int j = 0; j < nseeds; ++j) {
+      wire_operand_block(seeds[j], at / kWireBlockBytes, x[j]);
+      uint32_t a = 0;
+      for (uint32_t i = 0; i < kWireBlockElems; ++i) a = std::max<uint32_t>(a, x[j][i] & 0x7FFFu);
+      sb[j] = wire_scale_byte(a, f);
+    }
+    for (uint32_t i = 0; i < 16; ++i) {
+      uint32_t w[kMaxWireReduceSrcs];
+      for (int j = 0; j < nseeds; ++j) w[j] = x[j][2 * i] | static_cast<uint32_t>(x[j][2 * i + 1]) << 16;
+      sum[i] = wire_reduce_word(w, sb, nseeds, f);
+      amax = std::max(amax, wire_word_amax(sum[i]));
+    }
+    const uint32_t out_sb = wire_scale_byte(amax, f);
+    for (uint32_t c = 0; c < code_words; ++c) {
+      uint32_t got;
+      std::memcpy(&got, in + elems + 4 * c, 4);
+      r.checksum += got;
+      if (got != wire_code_word(sum + per * c, out_sb, f)) wrong(elems + 4 * c);
+    }
+    r.checksum += in[scale];
+    if (in[scale] != out_sb) wrong(scale);
+  });
+  return r;
+}
+
 namespace {
 
 void sockopts(int fd) {
@@ -389,6 +435,16 @@ class HostTransport final : public Transport {
       ops_.push_back({false, peers[i], scratch_.data() + i * image, image});
     }
   }
+  // --reduce-out wire: the same receives, the sum packed again in group_end().
+  VerifyResult verify_reduced_packed(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
+                                     WireFormat fmt) override {
+    return host_verify_wire_reduced_packed(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt);
+  }
+  void reduce_packed_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
+                          size_t src_offset, WireFormat fmt) override {
+    reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt);
+    wire_reduce_.packed = true;
+  }
 
   void group_begin() override {
     P2P_CHECK(!in_group_, "nested group");
@@ -428,7 +484,8 @@ class HostTransport final : public Transport {
       const size_t image = wire_bytes(wire_reduce_.bytes, wire_reduce_.fmt);
       std::vector<const void*> images{wire_reduce_.local_image};
       for (size_t i = 0; i < wire_reduce_.npeers; ++i) images.push_back(scratch_.data() + i * image);
-      host_wire_reduce(wire_reduce_.dst, images.data(), static_cast<int>(images.size()), wire_reduce_.bytes, wire_reduce_.fmt);
+      (wire_reduce_.packed ? host_wire_reduce_packed : host_wire_reduce)(wire_reduce_.dst, images.data(), static_cast<int>(images.size()),
+                                                                         wire_reduce_.bytes, wire_reduce_.fmt);
     }
     wire_reduce_ = {};
     // Injected skip fault: the images were read off the wire and are dropped.
@@ -459,6 +516,7 @@ class HostTransport final : public Transport {
     const void* local_image = nullptr;
     WireFormat fmt = WireFormat::Off;
     size_t npeers = 0;
+    bool packed = false;  // reduce_packed_from: dst receives the sum's wire image
   };
   struct PendingUnpack {
     void* dst;

@@ -341,6 +341,14 @@ class IpcTransport final : public GpuTransport {
       wire_reduce_.src[wire_reduce_.nsrc++] = static_cast<const char*>(reg->peer_send.ptr[static_cast<size_t>(peer)]) + src_offset;
     }
     wire_reduce_fmt_ = fmt;
+    wire_reduce_packed_ = false;
+  }
+  // --reduce-out wire: the same op, launched as the wire-reduce-pack kernel
+  // (kernels.hpp launch_wire_reduce_packed): dst receives the sum's image.
+  void reduce_packed_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
+                          size_t src_offset, WireFormat fmt) override {
+    reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt);
+    wire_reduce_packed_ = true;
   }
 
   void group_end() override {
@@ -498,7 +506,8 @@ class IpcTransport final : public GpuTransport {
       reduce_ = {};
     }
     if (wire_reduce_.dst) {
-      dev::launch_wire_reduce(wire_reduce_, wire_reduce_fmt_, stream_);
+      if (wire_reduce_packed_) dev::launch_wire_reduce_packed(wire_reduce_, wire_reduce_fmt_, stream_);
+      else dev::launch_wire_reduce(wire_reduce_, wire_reduce_fmt_, stream_);
       wire_reduce_ = {};
     }
     if (!unpack_ops_.empty()) {
@@ -676,6 +685,7 @@ class IpcTransport final : public GpuTransport {
   // Pull kernel: the open group's reduce_unpacked_from, launched in flush().
   dev::WireReduceOp wire_reduce_;
   WireFormat wire_reduce_fmt_ = WireFormat::Off;
+  bool wire_reduce_packed_ = false;  // posted by reduce_packed_from
   void* partial_ = nullptr;  // f32 planes of a wide bf16 sum (kernels.hpp reduce_partial_bytes)
   size_t partial_bytes_ = 0;
 

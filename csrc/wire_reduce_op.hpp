@@ -32,6 +32,25 @@
 // the sign of a zero on both sides: v_cvt_pk_bf16_f32 maps +-0 to +-0, and the
 // host's integer form adds 0x7FFF to 0x00000000 / 0x80000000, which carries
 // nothing into the upper half, so 0x0000 / 0x8000 come out.
+//
+// Requantised output (--reduce-out wire).  The output image of a hop that
+// forwards low precision is, by definition, wire_pack_block (same format as the
+// operands) of the bf16 sum above: the f32 chain is rounded once to bf16, and
+// that bf16 value is quantised under the no-clip scale of the block's bf16
+// amax.  No new rounding rule, and not a quantisation of the f32 sum: going
+// through bf16 makes the image bit-identical to packing the bf16 output, so a
+// chain of hops stays checkable.  Range: a non-zero sum lies in [2^-80, 2^-6),
+// so its bf16 rounding is zero or normal with exponent field in about
+// [47, 121] (rounding up can carry into the next binade, never further).  The
+// scale byte is then within [47 - 8, 121 - 1]: wire_scale_byte's clamp to
+// [1, 254] never acts.  A block whose sums are all zero (either sign) has
+// amax 0 and scale byte 127.  wire_quantize keeps the sign bit whatever the
+// magnitude, so a -0 sum is the code 0x80 / 0x8.  A block of sums may span
+// more binades than an operand block (16): cancellation leaves small sums next
+// to large ones, so the format's subnormals and zeros get more frequent under
+// the block's scale; wire_quantize covers those (its contract asks only for a
+// zero or normal bf16 and a quotient inside the format, which the no-clip
+// scale guarantees).
 #pragma once
 
 #include <cstddef>
@@ -60,5 +79,29 @@ void host_wire_reduce(void* out, const void* const* images, int k, size_t n, Wir
 // Compares p with the sum of the operand streams `seeds` (operand order), each
 // packed and unpacked by the shared functions; a wrong 32-bit word counts once.
 VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f);
+
+// ---- requantised output (--reduce-out wire) ----
+// The largest magnitude (bits & 0x7FFF) of the two bf16 halves of a sum word.
+P2P_HD uint32_t wire_word_amax(uint32_t w) {
+  const uint32_t lo = w & 0x7FFFu, hi = (w >> 16) & 0x7FFFu;
+  return lo > hi ? lo : hi;
+}
+// The codes of two sum words (4 elements, mxfp8: one word of 4 bytes) or of
+// four (8 elements, mxfp4: one word of 8 nibbles) under the block's scale byte.
+P2P_HD uint32_t wire_code_word(const uint32_t* w, uint32_t sb, WireFormat f) {
+  const int nw = f == WireFormat::Mxfp4 ? 4 : 2, bits = f == WireFormat::Mxfp4 ? 4 : 8;
+  uint32_t out = 0;
+  for (int i = 0; i < nw; ++i)
+    out |= (wire_quantize(w[i] & 0xFFFFu, sb, f) | (wire_quantize(w[i] >> 16, sb, f) << bits)) << (2 * bits * i);
+  return out;
+}
+// out_image: wire_bytes(n, f) bytes = the wire image (padding zeroed) of the
+// sum host_wire_reduce gives for the k images.  Any alignment.
+void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f);
+// Compares `image` with the packed sum of the operand streams `seeds`: a wrong
+// 32-bit word of element codes counts once, a wrong scale byte once, first_bad
+// is the lowest byte offset in the image of either, the checksum is the sum
+// of the code words and the scale bytes.  The padding is not read.
+VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f);
 
 }  // namespace p2p

@@ -388,6 +388,27 @@ def reference_wire_reduce(operands, fmt: str) -> torch.Tensor:
     return words_to_bytes(reference_reduce(widened, "bf16"))
 
 
+def wire_reduce_packed_(dst: torch.Tensor, srcs, nbytes: int, fmt: str, *, coherent: bool = False, max_blocks: int = 0,
+                        lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """``dst`` = the wire image (``wire_bytes(nbytes, fmt)`` bytes) of the bf16
+    sum :func:`wire_reduce_` gives for the 1..8 wire images ``srcs`` of
+    ``nbytes`` of payload each, with the gfx950 wire-reduce-pack kernel in one
+    launch (the IPC pull engine's receive under ``--reduce-out wire``)."""
+    nat = require_native()
+    image = nat.wire_bytes(nbytes, fmt)
+    if _check_tensor(dst) < image or any(_check_tensor(s) < image for s in srcs):
+        raise ValueError("wire_reduce_packed_: dst or a source holds less than wire_bytes() of the payload")
+    nat.wire_reduce_packed(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, fmt, _stream(stream), coherent, max_blocks, lanes)
+    return dst
+
+
+def reference_wire_reduce_packed(operands, fmt: str) -> torch.Tensor:
+    """What :func:`wire_reduce_packed_` leaves (uint8, the whole image):
+    :func:`reference_wire_pack` of the :func:`reference_wire_reduce` result."""
+    b = reference_wire_reduce(operands, fmt).to(torch.int64).reshape(-1, 4)
+    return reference_wire_pack(b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16) | (b[:, 3] << 24), fmt)
+
+
 # ---------------------------------------------------------------- diagnosis --
 
 class GranuleRecord(NamedTuple):
