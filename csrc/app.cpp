@@ -133,15 +133,15 @@ data
                          sum is checked bit for bit; flows are timed as ever (bytes pulled).
                          --transport ipc --ipc-engine kernel, or host; sizes multiples of 4;
                          not with --verify-inline, --diagnose, --reference or --resume
-      --wire FORMAT      mxfp8 | mxfp4: block-scaled payloads.  Payloads are bf16; the link
-                         carries their OCP microscaling image (8- or 4-bit elements, one
-                         power-of-two scale byte per 32 elements: 0.516 or 0.266 of the
-                         payload) and the receiver widens it back to bf16 as it pulls, in
+      --wire FORMAT      mxfp8 | mxfp6 | mxfp4: block-scaled payloads.  Payloads are bf16; the link
+                         carries their OCP microscaling image (8-, 6- (e2m3) or 4-bit elements,
+                         one power-of-two scale byte per 32 elements: 0.516, 0.391 or 0.266 of
+                         the payload) and the receiver widens it back to bf16 as it pulls, in
                          the gfx950 unpack kernel.  Flows are timed and reported in payload
                          bytes (the bf16 delivered); every kept slot is checked bit for bit.
                          --transport ipc --ipc-engine kernel, or host; sizes multiples of 64;
                          not with --reduce, --verify-inline, --diagnose, --reference or --resume
-      --reduce-wire FORMAT  mxfp8 | mxfp4, with --reduce bf16: every operand of a receiver's
+      --reduce-wire FORMAT  mxfp8 | mxfp6 | mxfp4, with --reduce bf16: every operand of a receiver's
                          sum is a block-scaled wire image (as --wire carries), its own shard
                          included.  The link moves the images; one launch of the gfx950
                          wire-reduce kernel dequantises them, adds them in f32 in operand
@@ -157,7 +157,8 @@ data
                          and stores a wire image in format F, ready to forward: bit for bit what
                          --reduce-out bf16 followed by a pack would give, without the bf16
                          round trip through memory.  Flows stay in payload bytes; the image is
-                         checked bit for bit.  Same transports and exclusions as --reduce-wire
+                         checked bit for bit.  Same transports and exclusions as --reduce-wire;
+                         F is mxfp8 or mxfp4 (mxfp6 sums to bf16 only)
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -417,14 +418,14 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     } else if (a == "--wire") {
       const std::string v = next();
       if (!parse_wire_format(v, &cfg->run.wire) || cfg->run.wire == WireFormat::Off) {
-        std::fprintf(stderr, "p2p_matrix: --wire '%s': the format is mxfp8 or mxfp4\n", v.c_str());
+        std::fprintf(stderr, "p2p_matrix: --wire '%s': the format is %s\n", v.c_str(), kWireFormatList);
         *exit_code = 1;
         return false;
       }
     } else if (a == "--reduce-wire") {
       const std::string v = next();
       if (!parse_wire_format(v, &cfg->run.reduce_wire) || cfg->run.reduce_wire == WireFormat::Off) {
-        std::fprintf(stderr, "p2p_matrix: --reduce-wire '%s': the format is mxfp8 or mxfp4\n", v.c_str());
+        std::fprintf(stderr, "p2p_matrix: --reduce-wire '%s': the format is %s\n", v.c_str(), kWireFormatList);
         *exit_code = 1;
         return false;
       }
@@ -583,6 +584,9 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     std::string why;
     if (cfg->run.reduce != ReduceType::Bf16 || cfg->run.reduce_wire == WireFormat::Off)
       why = "needs --reduce bf16 --reduce-wire FORMAT: the image it stores is the requantised sum of wire images, in their format";
+    if (why.empty() && cfg->run.reduce_wire == WireFormat::Mxfp6)
+      why = "cannot be combined with --reduce-wire mxfp6: 6-bit images are summed to bf16 only, their requantising epilogue "
+            "is not built (mxfp8 and mxfp4 have one)";
     if (why.empty() && !(cfg->transport == "host" || (cfg->transport == "ipc" && cfg->ipc_engine == "kernel")))
       why = strfmt("needs --transport ipc --ipc-engine kernel (the gfx950 wire-reduce-pack kernel) or --transport host; %s%s%s "
                    "sums no wire images", cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",

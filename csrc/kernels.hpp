@@ -230,7 +230,13 @@ void launch_verify_reduced(const void* p, size_t bytes, const uint64_t* seeds, i
 // payload_bytes is a multiple of 64 (a P2P_CHECK).  `lanes` picks the lane
 // mapping: Split (a lane's two units lie 4 KiB of payload apart, both stores
 // coalesced), Contiguous (one wider load, stores with a 32 B lane stride);
-// Auto is the one measured faster.
+// Auto is the one measured faster.  mxfp6 (24 B blocks, one block per lane and
+// v_cvt_scalef32_pk32_bf16_fp6; wire6_lane.hpp) maps `lanes` onto its own two
+// store paths: Contiguous is four 16 B stores straight from the lane (64 B
+// lane stride), Split sends the wave's 4 KiB through a wave-private LDS slot
+// and stores fully coalesced; Auto is Split.  The same holds for
+// launch_wire_reduce, whose mxfp6 kernel keeps 32 f32 accumulators per lane;
+// launch_wire_reduce_packed has no mxfp6 form and refuses the format.
 constexpr int kMaxUnpackOps = 32;
 enum class WireLanes : int { Auto = 0, Contiguous = 1, Split = 2 };
 struct UnpackOp {

@@ -136,16 +136,16 @@ class Session {
     P2P_CHECK(cfg.reduce == ReduceType::Off || (t_->supports_reduce() && bytes % 4 == 0 && !inline_check && diagnose <= 0),
               "reduce needs transport 'ipc' / 'ipc:kernel' or 'host', bytes a multiple of 4, and neither inline_check "
               "nor diagnose");
-    // wire="mxfp8" | "mxfp4": block-scaled payloads (runner.hpp RunConfig::wire).
+    // wire="mxfp8" | "mxfp6" | "mxfp4": block-scaled payloads (runner.hpp RunConfig::wire).
     P2P_CHECK(wire.empty() || (parse_wire_format(wire, &cfg.wire) && cfg.wire != WireFormat::Off),
-              "wire '" + wire + "': the format is mxfp8 or mxfp4");
+              "wire '" + wire + "': the format is " + kWireFormatList);
     P2P_CHECK(cfg.wire == WireFormat::Off || (t_->supports_wire() && bytes % kWireBlockBytes == 0 && reduce.empty() &&
                                               !inline_check && diagnose <= 0),
               "wire needs transport 'ipc' / 'ipc:kernel' or 'host', bytes a multiple of 64, and none of reduce, "
               "inline_check and diagnose");
-    // reduce_wire="mxfp8" | "mxfp4" with reduce="bf16": the operands are wire images (RunConfig::reduce_wire).
+    // reduce_wire="mxfp8" | "mxfp6" | "mxfp4" with reduce="bf16": the operands are wire images (RunConfig::reduce_wire).
     P2P_CHECK(reduce_wire.empty() || (parse_wire_format(reduce_wire, &cfg.reduce_wire) && cfg.reduce_wire != WireFormat::Off),
-              "reduce_wire '" + reduce_wire + "': the format is mxfp8 or mxfp4");
+              "reduce_wire '" + reduce_wire + "': the format is " + kWireFormatList);
     P2P_CHECK(cfg.reduce_wire == WireFormat::Off ||
                   (cfg.reduce == ReduceType::Bf16 && wire.empty() && t_->supports_reduce_wire() && bytes % kWireBlockBytes == 0),
               "reduce_wire needs reduce='bf16' (the format's payload is bf16), no wire, transport 'ipc' / 'ipc:kernel' or "
@@ -155,6 +155,8 @@ class Session {
     P2P_CHECK(reduce_out != "wire" || (cfg.reduce_wire != WireFormat::Off && !inline_check && diagnose <= 0),
               "reduce_out='wire' needs reduce='bf16' and reduce_wire (the image's format is the operands'), and neither "
               "inline_check nor diagnose");
+    P2P_CHECK(reduce_out != "wire" || cfg.reduce_wire != WireFormat::Mxfp6,
+              "reduce_out='wire' with reduce_wire='mxfp6': 6-bit images are summed to bf16 only (mxfp8 and mxfp4 requantise)");
     if (reduce_out == "wire") cfg.reduce_out = ReduceOut::Wire;
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
@@ -470,7 +472,7 @@ py::tuple device_verify_reduced(uintptr_t ptr, size_t bytes, const std::vector<u
 // ---- block-scaled wire formats (kernels.hpp UnpackOp, wire_op.hpp) on raw pointers ----
 WireFormat wire_format_arg(const std::string& name) {
   WireFormat f = WireFormat::Off;
-  if (!parse_wire_format(name, &f) || f == WireFormat::Off) throw py::value_error("wire: format '" + name + "' is not mxfp8 or mxfp4");
+  if (!parse_wire_format(name, &f) || f == WireFormat::Off) throw py::value_error("wire: format '" + name + "' is not " + kWireFormatList);
   return f;
 }
 size_t wire_payload_arg(size_t payload_bytes) {
@@ -515,7 +517,7 @@ py::tuple device_verify_unpacked(uintptr_t ptr, size_t payload_bytes, uint64_t s
 
 // ---- sum of wire images (kernels.hpp WireReduceOp) on raw pointers ----
 void device_wire_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t payload_bytes, const std::string& fmt,
-                        uintptr_t stream, bool coherent, int max_blocks, const std::string& lanes) {
+                        uintptr_t stream, const py::object& coherent, int max_blocks, const std::string& lanes) {
   const WireFormat f = wire_format_arg(fmt);
   if (srcs.empty() || srcs.size() > static_cast<size_t>(kMaxWireReduceSrcs))
     throw py::value_error("wire_reduce: 1..8 source images");
@@ -523,7 +525,15 @@ void device_wire_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_
   op.dst = reinterpret_cast<void*>(dst);
   op.payload_bytes = wire_payload_arg(payload_bytes);
   for (uintptr_t s : srcs) op.src[op.nsrc++] = reinterpret_cast<const void*>(s);
-  if (coherent) op.coherent_mask = (1u << op.nsrc) - 1u;
+  // A bool is every source; an int is WireReduceOp::coherent_mask, bit k for source k.
+  const uint32_t all = (1u << op.nsrc) - 1u;
+  if (py::isinstance<py::bool_>(coherent)) {
+    op.coherent_mask = coherent.cast<bool>() ? all : 0u;
+  } else {
+    const uint64_t mask = coherent.cast<uint64_t>();
+    if (mask & ~static_cast<uint64_t>(all)) throw py::value_error("wire_reduce: the coherent mask names a source the op does not have");
+    op.coherent_mask = static_cast<uint32_t>(mask);
+  }
   dev::launch_wire_reduce(op, f, as_stream(stream), max_blocks, wire_lanes_arg(lanes));
 }
 
@@ -1288,7 +1298,7 @@ PYBIND11_MODULE(_p2pcore, m) {
         dev::launch_pack(reinterpret_cast<void*>(dst), reinterpret_cast<const void*>(src), wire_payload_arg(payload_bytes),
                          wire_format_arg(fmt), as_stream(stream));
       }, py::arg("dst"), py::arg("src"), py::arg("payload_bytes"), py::arg("fmt"), py::arg("stream") = 0,
-      "The gfx950 pack kernel: payload_bytes of bf16 at src -> wire_bytes() of 'mxfp8' or 'mxfp4' at dst.");
+      "The gfx950 pack kernel: payload_bytes of bf16 at src -> wire_bytes() of 'mxfp8', 'mxfp6' or 'mxfp4' at dst.");
   m.def("wire_unpack", [](uintptr_t dst, uintptr_t src, size_t payload_bytes, const std::string& fmt, uintptr_t stream,
                           bool coherent, int max_blocks, const std::string& lanes) {
         device_wire_unpack_many({{dst, src, payload_bytes}}, fmt, stream, coherent, max_blocks, lanes);
@@ -1325,8 +1335,8 @@ PYBIND11_MODULE(_p2pcore, m) {
       }, py::arg("wire"), py::arg("payload_bytes"), py::arg("fmt"), "CPU unpack, bit-compatible with the unpack kernel.");
   m.def("wire_reduce", &device_wire_reduce, py::arg("dst"), py::arg("srcs"), py::arg("payload_bytes"), py::arg("fmt"),
         py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0, py::arg("lanes") = "auto",
-        "The IPC transport's gfx950 wire-reduce kernel: dst = payload_bytes of bf16, the f32 sum of the 1..8 'mxfp8' or "
-        "'mxfp4' wire images at srcs in that order, rounded once (coherent: every image read in the cross-GPU form; lanes: "
+        "The IPC transport's gfx950 wire-reduce kernel: dst = payload_bytes of bf16, the f32 sum of the 1..8 'mxfp8', 'mxfp6' or "
+        "'mxfp4' wire images at srcs in that order, rounded once (coherent: True reads every image in the cross-GPU form, an int is a mask, bit k for source k; lanes: "
         "'auto', 'contiguous' or 'split' lane mapping).");
   m.def("verify_wire_reduced", &device_verify_wire_reduced, py::arg("ptr"), py::arg("payload_bytes"), py::arg("seeds"),
         py::arg("fmt"), py::arg("stream") = 0,

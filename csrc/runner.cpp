@@ -637,6 +637,8 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   }
   P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Off,
             "reduce_out wire: only with reduce_wire (the image's format is the operands')");
+  P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Mxfp6,
+            "reduce_out wire: not with reduce_wire mxfp6 (6-bit images are summed to bf16 only)");
   if (cfg.wire != WireFormat::Off) {
     P2P_CHECK(t.supports_wire(), "wire: this transport cannot unpack a wire image (ipc with the kernel engine, or host)");
     P2P_CHECK(cfg.bytes % kWireBlockBytes == 0, "wire: the message size must be a multiple of 64");

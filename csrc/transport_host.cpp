@@ -112,13 +112,13 @@ void for_each_wire_block(size_t n, WireFormat f, Fn fn) {
   for (size_t tile = 0; tile * kWireTilePayload < n; ++tile) {
     const uint32_t nb = static_cast<uint32_t>(std::min<size_t>(kWireTileBlocks, (n - tile * kWireTilePayload) / kWireBlockBytes));
     for (uint32_t b = 0; b < nb; ++b)
-      fn(tile * kWireTilePayload + b * kWireBlockBytes, wire_at + b * eb, wire_at + nb * eb + b);
+      fn(tile * kWireTilePayload + b * kWireBlockBytes, wire_at + b * eb, wire_at + wire_tile_scale_offset(nb, f) + b);
     wire_at += wire_tile_bytes(nb, f);
   }
 }
 
 void check_wire(size_t n, WireFormat f, const char* who) {
-  P2P_CHECK(f == WireFormat::Mxfp8 || f == WireFormat::Mxfp4, std::string(who) + ": the format is mxfp8 or mxfp4");
+  P2P_CHECK(wire_format_valid(f), std::string(who) + ": the format is " + kWireFormatList);
   P2P_CHECK(n % kWireBlockBytes == 0, std::string(who) + ": the payload is a multiple of 64 bytes (blocks of 32 bf16)");
 }
 
@@ -239,6 +239,7 @@ VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* s
 // ---- the same sum, requantised (wire_reduce_op.hpp) ----
 void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f) {
   check_wire(n, f, "host_wire_reduce_packed");
+  P2P_CHECK(f != WireFormat::Mxfp6, "host_wire_reduce_packed: mxfp6 images are summed to bf16 only (no requantised output yet)");
   std::vector<char> sum(n);
   host_wire_reduce(sum.data(), images, k, n, f);
   host_wire_pack(out_image, sum.data(), n, f);
@@ -246,6 +247,7 @@ void host_wire_reduce_packed(void* out_image, const void* const* images, int k, 
 
 VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f) {
   check_wire(n, f, "host_verify_wire_reduced_packed");
+  P2P_CHECK(f != WireFormat::Mxfp6, "host_verify_wire_reduced_packed: mxfp6 images are summed to bf16 only (no requantised output yet)");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "host_verify_wire_reduced_packed: 1..8 operand seeds");
   const auto* in = static_cast<const uint8_t*>(image);
   const uint32_t code_words = wire_block_elem_bytes(f) / 4, per = 16 / code_words;  // sum words per word of codes

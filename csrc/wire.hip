@@ -1,5 +1,5 @@
 // gfx950 kernels of the block-scaled wire formats (--wire): the pull engine's
-// receive that widens MXFP8 / MXFP4 to bf16, the sender's pack (from bf16 or
+// receive that widens MXFP8 / MXFP6 / MXFP4 to bf16, the sender's pack (from bf16 or
 // straight from the operand stream) and the check of an unpacked buffer.
 // kernels.hpp has the contract, wire_op.hpp the format and the arithmetic.
 // Design:
@@ -23,6 +23,9 @@
 //   * Pack: amax is an integer max of magnitudes in the lane, one xor shuffle
 //     across the 2 lanes of an mxfp8 block; the scale bytes of a tile are
 //     staged in LDS and leave as 16 B stores of 8 lanes.
+//   * mxfp6 converts a whole block per lane and instruction, so it has
+//     kernels of its own below (multi_unpack6_kernel, pack6_kernel) behind the
+//     same launchers; wire6_lane.hpp has their design.
 //   * No packed f32 instructions in this object (Makefile).
 #include <hip/hip_runtime.h>
 
@@ -33,6 +36,7 @@
 #include "common.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
+#include "wire6_lane.hpp"
 
 namespace p2p {
 namespace dev {
@@ -49,16 +53,16 @@ constexpr int kWaves = kBlock / 64;
 constexpr uint64_t kMaxGrid = 1ull << 20;  // tiles per grid pass (8 GiB of payload)
 constexpr int kVerifyPerCu = 16;           // verify_unpacked: workgroups per CU, grid-stride beyond
 constexpr int kPackPerCu = 16;
-// Cache-policy bits and descriptor word of the cross-GPU accesses (kernels.hip).
-constexpr int kSystemCoherent = 1 | 16;  // sc0 sc1
-constexpr int kRsrcFlags = 0x00020000;
+// Cache-policy bits, descriptor word and scale operand: one definition for this file and wire_reduce.hip.
+using wire6::kRsrcFlags;
+using wire6::kSystemCoherent;
 
 // The narrowing instructions divide by their scale operand and round to
 // nearest even, the target's subnormals included: compared on a GPU, they
 // agree with wire_quantize on every bf16 under every scale byte for which
 // the quotient is inside the format (docs/DESIGN.md), so no step of the pack
 // needs the integer arithmetic.
-__device__ __forceinline__ float scale_operand(uint32_t sb) { return __builtin_bit_cast(float, sb << 23); }
+using wire6::scale_operand;
 
 // ------------------------------------------------------------------ unpack ----
 
@@ -185,6 +189,58 @@ __global__ __launch_bounds__(kBlock) void multi_unpack_kernel(const UnpackArgs a
   }
 }
 
+// mxfp6: a lane owns a block (wire6_lane.hpp has the geometry and the store
+// paths).  The same op table, lookup and grid-stride passes; a workgroup's
+// pass is kTilesPerGroup tiles, and its waves never meet: no barrier.
+template <bool SPLIT>
+__global__ __launch_bounds__(wire6::kLanes) void multi_unpack6_kernel(const UnpackArgs a) {
+  using wire6::kF, wire6::kEB, wire6::kFullTile, wire6::kLanes, wire6::kTilesPerGroup, wire6::kSlotBytes, wire6::kTileLanes;
+  using wire6::u32x6, wire6::u32x16, wire6::load_codes, wire6::store_block;
+  __shared__ __attribute__((aligned(16))) char slots[SPLIT ? (kLanes / 64) * kSlotBytes : 16];
+  int op = 0;
+  if (a.uniform > 0) {
+    op = min(static_cast<int>(blockIdx.x / static_cast<uint32_t>(a.uniform)), a.nops - 1);
+  } else {
+    int lo = 0, hi = a.nops - 1;  // largest op with block_begin[op] <= blockIdx.x
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (blockIdx.x >= a.block_begin[mid]) lo = mid; else hi = mid - 1;
+    }
+    op = lo;
+  }
+  const uint32_t b = blockIdx.x - a.block_begin[op];
+  const uint32_t nwg = a.block_begin[op + 1] - a.block_begin[op];
+  const uint64_t ntiles = a.ntiles[op];
+  const bool src_coh = (a.src_coherent >> op) & 1u, dst_coh = (a.dst_coherent >> op) & 1u;
+  // The wave index as a scalar: the tile, its descriptors and the loop are uniform per wave.
+  const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t wave_block = 64u * (wave % (kTileLanes / 64u));  // 0 or 64
+  const uint32_t blk = wave_block + lane;                         // the lane's block of its tile
+  char* slot = slots + (SPLIT ? wave * kSlotBytes : 0);
+
+  for (uint64_t t = static_cast<uint64_t>(b) * kTilesPerGroup + wave / (kTileLanes / 64u); t < ntiles;
+       t += static_cast<uint64_t>(nwg) * kTilesPerGroup) {
+    // Uniform per wave: the tile's blocks and the ranges of its descriptors.
+    const uint32_t nb = t + 1 == ntiles ? a.last_blocks[op] : kWireTileBlocks;
+    const uint32_t soff = wire_tile_scale_offset(nb, kF);
+    const char* ws = a.src[op] + t * kFullTile;
+    const bool in = blk < nb;
+    u32x6 codes;
+    uint32_t sb;
+    if (src_coh) {
+      auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(ws), 0, static_cast<int>(soff + nb), kRsrcFlags);
+      codes = load_codes<kSystemCoherent>(rs, static_cast<int>(in ? kEB * blk : soff + nb));
+      sb = __builtin_amdgcn_raw_buffer_load_b8(rs, static_cast<int>(soff + blk), 0, kSystemCoherent);
+    } else {
+      codes = load_codes(ws + (in ? kEB * blk : 0));
+      sb = reinterpret_cast<const uint8_t*>(ws + soff)[in ? blk : 0];
+    }
+    const u32x16 r = __builtin_bit_cast(u32x16, __builtin_amdgcn_cvt_scalef32_pk32_bf16_fp6(codes, scale_operand(sb)));
+    const u32x4 v[4] = {{r[0], r[1], r[2], r[3]}, {r[4], r[5], r[6], r[7]}, {r[8], r[9], r[10], r[11]}, {r[12], r[13], r[14], r[15]}};
+    store_block<SPLIT>(v, a.dst[op] + t * kWireTilePayload, nb, wave_block, lane, dst_coh, slot);
+  }
+}
+
 // -------------------------------------------------------------------- pack ----
 
 // Two bf16 words (4 elements, mxfp8) or four (8 elements, mxfp4) -> one word of codes.
@@ -260,6 +316,56 @@ __global__ __launch_bounds__(pack_lanes<F>()) void pack_kernel(const u32x4* __re
   }
 }
 
+// mxfp6: a lane owns a block and a 128-lane workgroup a tile.  16 payload
+// words per lane, the amax entirely in the lane, one
+// v_cvt_scalef32_pk32_fp6_bf16, 24 B of codes at a 24 B lane stride (three
+// 8 B stores; a wave's codes are contiguous).  The 8 B of zeros behind an odd
+// tile's element section come from lane 0, the scale bytes and the zeros
+// behind them through LDS as 16 B stores.  Not tuned: it is the sender's step.
+template <bool FROM_PRNG>
+__global__ __launch_bounds__(wire6::kTileLanes) void pack6_kernel(const u32x4* __restrict__ payload, char* __restrict__ wire,
+                                                                  uint64_t ntiles, uint32_t last_blocks, uint64_t seed) {
+  using wire6::kF, wire6::kEB, wire6::kFullTile, wire6::u32x6, wire6::u32x16, wire6::bf16x32;
+  __shared__ __attribute__((aligned(16))) uint8_t scales[kWireTileBlocks];
+  const uint32_t L = threadIdx.x;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint32_t nb = t + 1 == ntiles ? last_blocks : kWireTileBlocks;
+    const bool mine = L < nb;
+    u32x16 w;
+    if constexpr (FROM_PRNG) {
+      const uint64_t word0 = t * (kWireTilePayload / 4);  // a tile never straddles a 2^32-word key span
+      const uint32_t key = prng_key(seed, word0);         // block-uniform: scalar ALU
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const uint64_t at = word0 + 16 * L + i;
+        w[i] = wire_operand_word(prng_word_k(key, static_cast<uint32_t>(at)), at);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {  // a lane past the end re-reads the tile's first block
+        const u32x4 v = __builtin_nontemporal_load(payload + t * (kWireTilePayload / 16) + (mine ? 4 * L + i : i));
+        w[4 * i] = v[0], w[4 * i + 1] = v[1], w[4 * i + 2] = v[2], w[4 * i + 3] = v[3];
+      }
+    }
+    uint32_t amax = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) amax = max(amax, max(w[i] & 0x7FFFu, (w[i] >> 16) & 0x7FFFu));
+    const uint32_t sb = wire_scale_byte(amax, kF);
+    const u32x6 c = __builtin_amdgcn_cvt_scalef32_pk32_fp6_bf16(__builtin_bit_cast(bf16x32, w), scale_operand(sb));
+    char* wt = wire + t * kFullTile;
+    if (mine) {
+      auto* out = reinterpret_cast<u32x2*>(wt + kEB * L);
+      out[0] = u32x2{c[0], c[1]}, out[1] = u32x2{c[2], c[3]}, out[2] = u32x2{c[4], c[5]};
+    }
+    if (L == 0 && (nb & 1u)) *reinterpret_cast<u32x2*>(wt + kEB * nb) = u32x2{0, 0};
+    scales[L] = mine ? static_cast<uint8_t>(sb) : 0;
+    __syncthreads();
+    if (L < 8 && 16 * L < nb)
+      *reinterpret_cast<u32x4*>(wt + wire_tile_scale_offset(nb, kF) + 16 * L) = *reinterpret_cast<const u32x4*>(scales + 16 * L);
+    __syncthreads();
+  }
+}
+
 // --------------------------------------------------------- verify unpacked ----
 
 struct Partial {
@@ -327,7 +433,7 @@ __global__ __launch_bounds__(kBlock) void verify_unpacked_kernel(const uint4* __
 // ------------------------------------------------------------------ launch ----
 
 void check_format(WireFormat f, size_t n, const char* who) {
-  P2P_CHECK(f == WireFormat::Mxfp8 || f == WireFormat::Mxfp4, std::string(who) + ": the format is mxfp8 or mxfp4");
+  P2P_CHECK(wire_format_valid(f), std::string(who) + ": the format is " + kWireFormatList);
   P2P_CHECK(n % kWireBlockBytes == 0, std::string(who) + ": the payload must be a multiple of 64 bytes (blocks of 32 bf16)");
 }
 
@@ -354,13 +460,16 @@ void launch_unpack_group(const UnpackOp* ops, int cnt, WireFormat fmt, hipStream
     if (o.dst_coherent) a.dst_coherent |= 1u << i;
   }
   const uint64_t cap = max_blocks > 0 ? static_cast<uint64_t>(max_blocks) : kMaxGrid;
-  const uint32_t grid = split_blocks(a.ntiles, cnt, 1, cap, a.block_begin);
+  const uint32_t grid = split_blocks(a.ntiles, cnt, fmt == WireFormat::Mxfp6 ? wire6::kTilesPerGroup : 1, cap, a.block_begin);
   a.uniform = static_cast<int32_t>(a.block_begin[1] - a.block_begin[0]);
   for (int i = 1; i < cnt; ++i)
     if (a.block_begin[i + 1] - a.block_begin[i] != static_cast<uint32_t>(a.uniform)) a.uniform = 0;
   // Auto: the mapping measured faster per format (docs/DESIGN.md).
   const bool split = lanes == WireLanes::Auto ? true : lanes == WireLanes::Split;
-  if (fmt == WireFormat::Mxfp8) {
+  if (fmt == WireFormat::Mxfp6) {
+    if (split) multi_unpack6_kernel<true><<<grid, wire6::kLanes, 0, stream>>>(a);
+    else multi_unpack6_kernel<false><<<grid, wire6::kLanes, 0, stream>>>(a);
+  } else if (fmt == WireFormat::Mxfp8) {
     if (split) multi_unpack_kernel<WireFormat::Mxfp8, true><<<grid, kBlock, 0, stream>>>(a);
     else multi_unpack_kernel<WireFormat::Mxfp8, false><<<grid, kBlock, 0, stream>>>(a);
   } else {
@@ -380,7 +489,9 @@ void launch_pack_impl(void* wire, const void* payload, size_t n, uint64_t seed, 
   const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(ntiles, static_cast<uint64_t>(cu_count()) * kPackPerCu));
   const auto* src = static_cast<const u32x4*>(payload);
   auto* dst = static_cast<char*>(wire);
-  if (fmt == WireFormat::Mxfp8)
+  if (fmt == WireFormat::Mxfp6)
+    pack6_kernel<FROM_PRNG><<<grid, wire6::kTileLanes, 0, stream>>>(src, dst, ntiles, last_blocks_of(n), seed);
+  else if (fmt == WireFormat::Mxfp8)
     pack_kernel<WireFormat::Mxfp8, FROM_PRNG><<<grid, pack_lanes<WireFormat::Mxfp8>(), 0, stream>>>(src, dst, ntiles, last_blocks_of(n), seed);
   else
     pack_kernel<WireFormat::Mxfp4, FROM_PRNG><<<grid, pack_lanes<WireFormat::Mxfp4>(), 0, stream>>>(src, dst, ntiles, last_blocks_of(n), seed);
@@ -413,6 +524,8 @@ void launch_verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, 
     const auto* vp = static_cast<const uint4*>(p);
     if (fmt == WireFormat::Mxfp8)
       verify_unpacked_kernel<WireFormat::Mxfp8><<<grid, kBlock, 0, stream>>>(vp, nvec, seed, acc);
+    else if (fmt == WireFormat::Mxfp6)
+      verify_unpacked_kernel<WireFormat::Mxfp6><<<grid, kBlock, 0, stream>>>(vp, nvec, seed, acc);
     else
       verify_unpacked_kernel<WireFormat::Mxfp4><<<grid, kBlock, 0, stream>>>(vp, nvec, seed, acc);
     HIPCHECK(hipGetLastError());

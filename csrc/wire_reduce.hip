@@ -28,7 +28,10 @@
 //     scale byte per source), stores with a 32 B lane stride.
 //   * Scale bytes: one byte load per lane, unit and source.  No LDS: every
 //     byte is used once.
-//   * No packed f32 instructions in this object (Makefile): the 16 add chains
+//   * mxfp6 widens a whole block per lane and instruction: wire_reduce6_kernel
+//     below, a lane per block and 32 accumulators, behind the same launcher;
+//     wire6_lane.hpp has its geometry and its two store paths.
+//   * No packed f32 instructions in this object (Makefile): the add chains
 //     stay scalar f32 adds.
 #include <hip/hip_runtime.h>
 
@@ -37,6 +40,7 @@
 #include "common.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
+#include "wire6_lane.hpp"
 
 namespace p2p {
 namespace dev {
@@ -51,10 +55,10 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr uint64_t kMaxGrid = 1ull << 20;  // tiles per grid pass (8 GiB of payload)
 constexpr int kVerifyPerCu = 16;           // verify_wire_reduced: workgroups per CU, grid-stride beyond
-// Cache-policy bits and descriptor word of the cross-GPU accesses (kernels.hip).
-constexpr int kSystemCoherent = 1 | 16;  // sc0 sc1
-constexpr int kNonTemporal = 2;           // nt
-constexpr int kRsrcFlags = 0x00020000;
+// Cache-policy bits, descriptor word and scale operand: one definition for this file and wire.hip.
+using wire6::kNonTemporal;
+using wire6::kRsrcFlags;
+using wire6::kSystemCoherent;
 
 // By value in the kernarg segment.
 struct WireReduceArgs {
@@ -65,7 +69,7 @@ struct WireReduceArgs {
   uint32_t coherent;     // WireReduceOp::coherent_mask
 };
 
-__device__ __forceinline__ float scale_operand(uint32_t sb) { return __builtin_bit_cast(float, sb << 23); }
+using wire6::scale_operand;
 
 // 8 codes (mxfp8: w[0] and w[1]; mxfp4: w[0]) under one scale -> 8 f32.
 template <WireFormat F>
@@ -197,6 +201,70 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_kernel(const WireReduceArg
   }
 }
 
+// mxfp6: a lane owns a block (wire6_lane.hpp has the geometry and the store
+// paths).  The K x (three 8 B code loads + one scale byte load) of a block are
+// issued before the first conversion; v_cvt_scalef32_pk32_f32_fp6 widens an
+// operand's 32 codes at once, 32 plain v_add_f32 per further operand in
+// operand order, 16 v_cvt_pk_bf16_f32.  Registers at K = 8: 48 of codes, 8
+// scale bytes, 32 accumulators and 32 of the operand being widened.
+template <int K, bool SPLIT>
+__global__ __launch_bounds__(wire6::kLanes) void wire_reduce6_kernel(const WireReduceArgs a) {
+  using wire6::kF, wire6::kEB, wire6::kFullTile, wire6::kLanes, wire6::kTilesPerGroup, wire6::kSlotBytes, wire6::kTileLanes;
+  using wire6::u32x6, wire6::f32x32, wire6::load_codes, wire6::store_block;
+  __shared__ __attribute__((aligned(16))) char slots[SPLIT ? (kLanes / 64) * kSlotBytes : 16];
+  // The wave index as a scalar: the tile, its descriptors and the loop are uniform per wave.
+  const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t wave_block = 64u * (wave % (kTileLanes / 64u));  // 0 or 64
+  const uint32_t blk = wave_block + lane;                         // the lane's block of its tile
+  char* slot = slots + (SPLIT ? wave * kSlotBytes : 0);
+
+  for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kTilesPerGroup + wave / (kTileLanes / 64u); t < a.ntiles;
+       t += static_cast<uint64_t>(gridDim.x) * kTilesPerGroup) {
+    const uint32_t nb = t + 1 == a.ntiles ? a.last_blocks : kWireTileBlocks;
+    const uint32_t soff = wire_tile_scale_offset(nb, kF);
+    const bool in = blk < nb;
+    u32x6 codes[K];
+    uint32_t sb[K];
+    if ((a.coherent & ((1u << K) - 1u)) == 0) {
+      // Every image is local: a lane past the tile's end re-reads its first block.
+      const uint32_t at = in ? kEB * blk : 0, sat = soff + (in ? blk : 0);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const char* ws = a.src[k] + t * kFullTile;
+        codes[k] = load_codes(ws + at);
+        sb[k] = reinterpret_cast<const uint8_t*>(ws)[sat];
+      }
+    } else {
+      // One range-checked descriptor per source and tile; a lane past the end
+      // aims at its end and loads 0.  The uniform branch picks the cache policy.
+      const int at = static_cast<int>(in ? kEB * blk : soff + nb), sat = static_cast<int>(soff + blk);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.src[k] + t * kFullTile), 0,
+                                                    static_cast<int>(soff + nb), kRsrcFlags);
+        if ((a.coherent >> k) & 1u) {
+          codes[k] = load_codes<kSystemCoherent>(rs, at);
+          sb[k] = __builtin_amdgcn_raw_buffer_load_b8(rs, sat, 0, kSystemCoherent);
+        } else {
+          codes[k] = load_codes<kNonTemporal>(rs, at);
+          sb[k] = __builtin_amdgcn_raw_buffer_load_b8(rs, sat, 0, kNonTemporal);
+        }
+      }
+    }
+    f32x32 acc = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(codes[0], scale_operand(sb[0]));
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+      const f32x32 x = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(codes[k], scale_operand(sb[k]));
+#pragma unroll
+      for (int j = 0; j < 32; ++j) acc[j] = acc[j] + x[j];
+    }
+    u32x4 v[4];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j / 4][j % 4] = reduce_pack_bf16(acc[2 * j], acc[2 * j + 1]);
+    store_block<SPLIT>(v, a.dst + t * kWireTilePayload, nb, wave_block, lane, false, slot);
+  }
+}
+
 // ------------------------------------------------------------------ verify ----
 
 struct SeedArgs {
@@ -278,7 +346,7 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_kernel(const uint4
 // ------------------------------------------------------------------ launch ----
 
 void check_format(WireFormat f, size_t n, const char* who) {
-  P2P_CHECK(f == WireFormat::Mxfp8 || f == WireFormat::Mxfp4, std::string(who) + ": the format is mxfp8 or mxfp4");
+  P2P_CHECK(wire_format_valid(f), std::string(who) + ": the format is " + kWireFormatList);
   P2P_CHECK(n % kWireBlockBytes == 0, std::string(who) + ": the payload must be a multiple of 64 bytes (blocks of 32 bf16)");
 }
 
@@ -287,10 +355,12 @@ void launch_wire_reduce_k(int nsrc, uint32_t grid, const WireReduceArgs& a, hipS
   if constexpr (K < 1) {
     P2P_FATAL("wire_reduce: an op needs 1..8 sources");
   } else {
-    if (nsrc == K)
-      wire_reduce_kernel<F, K, SPLIT><<<grid, kBlock, 0, stream>>>(a);
-    else
+    if (nsrc != K)
       launch_wire_reduce_k<F, SPLIT, K - 1>(nsrc, grid, a, stream);
+    else if constexpr (F == WireFormat::Mxfp6)
+      wire_reduce6_kernel<K, SPLIT><<<(grid + wire6::kTilesPerGroup - 1) / wire6::kTilesPerGroup, wire6::kLanes, 0, stream>>>(a);
+    else
+      wire_reduce_kernel<F, K, SPLIT><<<grid, kBlock, 0, stream>>>(a);
   }
 }
 
@@ -313,9 +383,12 @@ void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stre
   a.coherent = op.coherent_mask;
   const uint64_t cap = max_blocks > 0 ? static_cast<uint64_t>(max_blocks) : kMaxGrid;
   const uint32_t grid = static_cast<uint32_t>(std::min(a.ntiles, cap));
-  // Auto: split was measured faster, or level, for both formats at every fan-in (docs/DESIGN.md).
+  // Auto: split was measured faster, or level, for every format at every fan-in (docs/DESIGN.md).
   const bool split = lanes == WireLanes::Auto ? true : lanes == WireLanes::Split;
-  if (fmt == WireFormat::Mxfp8) {
+  if (fmt == WireFormat::Mxfp6) {
+    if (split) launch_wire_reduce_k<WireFormat::Mxfp6, true>(op.nsrc, grid, a, stream);
+    else launch_wire_reduce_k<WireFormat::Mxfp6, false>(op.nsrc, grid, a, stream);
+  } else if (fmt == WireFormat::Mxfp8) {
     if (split) launch_wire_reduce_k<WireFormat::Mxfp8, true>(op.nsrc, grid, a, stream);
     else launch_wire_reduce_k<WireFormat::Mxfp8, false>(op.nsrc, grid, a, stream);
   } else {
@@ -340,6 +413,8 @@ void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint6
     const auto* vp = static_cast<const uint4*>(p);
     if (fmt == WireFormat::Mxfp8)
       verify_wire_reduced_kernel<WireFormat::Mxfp8><<<grid, kBlock, 0, stream>>>(vp, nvec, s, acc);
+    else if (fmt == WireFormat::Mxfp6)
+      verify_wire_reduced_kernel<WireFormat::Mxfp6><<<grid, kBlock, 0, stream>>>(vp, nvec, s, acc);
     else
       verify_wire_reduced_kernel<WireFormat::Mxfp4><<<grid, kBlock, 0, stream>>>(vp, nvec, s, acc);
     HIPCHECK(hipGetLastError());

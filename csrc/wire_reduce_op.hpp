@@ -1,5 +1,5 @@
 // Receive-and-reduce of block-scaled operands (--reduce-wire): every operand of
-// a receiver's sum is an MXFP8 / MXFP4 wire image (wire_op.hpp: format, tiles,
+// a receiver's sum is an MXFP8 / MXFP6 / MXFP4 wire image (wire_op.hpp: format, tiles,
 // scale rule), the sum leaves as bf16.  Shared by the gfx950 kernels
 // (wire_reduce.hip), the host transport and the host-side regeneration of
 // expected values, so all of them produce the same bits.  Nothing new is
@@ -22,10 +22,14 @@
 // = 2^-9, and kMaxWireReduceSrcs = 8 of them stay below 2^-6: nothing
 // overflows.  No add produces or consumes a subnormal, so the device's
 // denormal mode cannot change a bit, and the single bf16 rounding sees a
-// normal f32 or a zero.
+// normal f32 or a zero.  mxfp6 (e2m3) has mxfp4's exponent range: its scale
+// byte is >= 64 - 2 = 62 and <= 109, its smallest non-zero magnitude is the
+// subnormal step 0.125 x 2^(62 - 127) = 2^-68, every partial sum a multiple of
+// it, and its largest operand 7.5 x 2^(109 - 127) < 2^-15, so eight of them
+// stay below 2^-12: the same argument holds with room to spare.
 //
 // Zeros are real operands here, unlike in reduce_op.hpp: the codes 0x00 / 0x80
-// (mxfp8) and 0x0 / 0x8 (mxfp4) occur, and the sign of a zero is kept by the
+// (mxfp8), 0x00 / 0x20 (mxfp6) and 0x0 / 0x8 (mxfp4) occur, and the sign of a zero is kept by the
 // dequantisation.  Signed zeros follow IEEE addition in round-to-nearest:
 // (+0) + (-0) = +0, (-0) + (-0) = -0, and an exact cancellation x + (-x) gives
 // +0.  A single operand passes through with its sign.  reduce_pack_bf16 keeps

@@ -383,7 +383,7 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_packed_kernel(cons
 // ------------------------------------------------------------------ launch ----
 
 void check_format(WireFormat f, size_t n, const char* who) {
-  P2P_CHECK(f == WireFormat::Mxfp8 || f == WireFormat::Mxfp4, std::string(who) + ": the format is mxfp8 or mxfp4");
+  P2P_CHECK(f == WireFormat::Mxfp8 || f == WireFormat::Mxfp4, std::string(who) + ": the format is mxfp8 or mxfp4 (mxfp6 images are summed to bf16 only)");
   P2P_CHECK(n % kWireBlockBytes == 0, std::string(who) + ": the payload must be a multiple of 64 bytes (blocks of 32 bf16)");
 }
 

@@ -3,7 +3,7 @@
 and native.wire_pack against the plain copy kernel, in one process and one window.
 
 For each shape (32 MiB x 32 ops, 1 GiB x 1; payload bytes), format (mxfp8,
-mxfp4) and access form (non-temporal, cross-GPU coherent on local memory): a
+mxfp6, mxfp4; --formats picks) and access form (non-temporal, cross-GPU coherent on local memory): a
 sustained warm-up, then 20 rounds in which the plain copy of the payload
 (native.copy_many), the unpack in both lane mappings (split, contiguous) and
 the pack take turns, each launch (the pack: one launch per op) between its
@@ -32,7 +32,7 @@ from copy_checked_bench import alternate, warm  # noqa: E402
 
 MIB = 1 << 20
 SHAPES = [("32MiB x 32", 32 * MIB, 32), ("1GiB x 1", 1024 * MIB, 1)]
-FORMATS = ("mxfp8", "mxfp4")
+FORMATS = ("mxfp8", "mxfp6", "mxfp4")
 
 
 def main():
@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--json", help="write the records here")
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warm-seconds", type=float, default=0.3)
+    ap.add_argument("--formats", default=",".join(FORMATS), help="comma-separated subset of " + ", ".join(FORMATS))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("wire_bench: needs a GPU (no rate is reported without one)")
@@ -52,7 +53,7 @@ def main():
         dst = [torch.empty(nbytes, dtype=torch.uint8, device="cuda") for _ in range(nops)]
         src = [torch.empty(nbytes, dtype=torch.uint8, device="cuda") for _ in range(nops)]  # the copy's source, the pack's payload
         copy_ops = [(d.data_ptr(), s.data_ptr(), nbytes) for d, s in zip(dst, src)]
-        for fmt in FORMATS:
+        for fmt in args.formats.split(","):
             wb = nat.wire_bytes(nbytes, fmt)
             wire = [torch.empty(wb, dtype=torch.uint8, device="cuda") for _ in range(nops)]
             packed = [torch.empty(wb, dtype=torch.uint8, device="cuda") for _ in range(nops)]

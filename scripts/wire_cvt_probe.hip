@@ -3,12 +3,94 @@
 // Narrowing: every normal bf16 under every scale byte for which the quotient is inside the
 // format, with the scale operand 2^e (divides) and 2^-e (multiplies); widening: every code under
 // every scale byte with a normal result.  Prints the mismatch counts and a few examples.
+// The 6-bit block instructions (pk32: 32 elements, 6 VGPRs of codes) are probed with the value
+// under test at a varying element position among 31 markers, which also settles their register
+// layout: element j in bits 6j .. 6j + 5 of the 6 VGPRs read as one little-endian integer.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "wire_op.hpp"
 using namespace p2p;
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
+
+typedef unsigned int u32x6 __attribute__((ext_vector_type(6)));
+typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
+typedef float f32x32 __attribute__((ext_vector_type(32)));
+typedef unsigned int u32x32 __attribute__((ext_vector_type(32)));
+
+struct Out6 {
+  unsigned long long nbad[2], ntotal;      // narrow: [mode]
+  unsigned long long wbad[2], wtotal;      // widen: [0: to bf16, 1: to f32]
+  unsigned int nex[8][4], nnex, wex[8][4], wnex;
+};
+
+__device__ void put_code(u32x6& c, unsigned pos, unsigned code) {
+  const unsigned bit = 6 * pos, w = bit >> 5, sh = bit & 31;
+  c[w] = (c[w] & ~(0x3Fu << sh)) | (code << sh);
+  if (sh > 26) c[w + 1] = (c[w + 1] & ~(0x3Fu >> (32 - sh))) | (code >> (32 - sh));
+}
+__device__ unsigned get_code(const u32x6& c, unsigned pos) {
+  const unsigned bit = 6 * pos, w = bit >> 5, sh = bit & 31;
+  unsigned v = c[w] >> sh;
+  if (sh > 26) v |= c[w + 1] << (32 - sh);
+  return v & 0x3Fu;
+}
+
+__global__ void narrow6_probe(Out6* o) {
+  const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;  // x (16 bits) | sb (8 bits) << 16
+  const unsigned x = gid & 0xFFFF, sb = gid >> 16;
+  if (sb < 1 || sb > 254) return;
+  const int ex = (x >> 7) & 0xFF, m = x & 0x7F;
+  if (ex == 255 || (ex == 0 && m)) return;  // zero or normal
+  const int k = ex - (int)sb;
+  if (ex && (!(k < 2 || (k == 2 && m <= 0x70)) || k < -40)) return;
+  const unsigned want = wire_quantize(x, sb, WireFormat::Mxfp6), pos = (x ^ (x >> 5) ^ sb) & 31;
+  atomicAdd(&o->ntotal, 1ull);
+  for (int mode = 0; mode < 2; ++mode) {
+    const float scale = __builtin_bit_cast(float, (mode ? 254u - sb : sb) << 23);
+    u32x16 w;
+    for (int i = 0; i < 16; ++i) w[i] = 0;  // markers: +0 everywhere else
+    w[pos >> 1] = x << (16 * (pos & 1));
+    const u32x6 c = __builtin_amdgcn_cvt_scalef32_pk32_fp6_bf16(__builtin_bit_cast(bf16x32, w), scale);
+    bool ok = true;
+    for (unsigned j = 0; j < 32; ++j) ok = ok && get_code(c, j) == (j == pos ? want : 0u);
+    if (!ok) {
+      atomicAdd(&o->nbad[mode], 1ull);
+      if (mode == 0) {
+        const unsigned n = atomicAdd(&o->nnex, 1u);
+        if (n < 8) { o->nex[n][0] = x; o->nex[n][1] = sb; o->nex[n][2] = get_code(c, pos); o->nex[n][3] = want; }
+      }
+    }
+  }
+}
+
+__global__ void widen6_probe(Out6* o) {
+  const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;  // code (6 bits) | pos (5 bits) << 6 | sb << 11
+  const unsigned code = gid & 63, pos = (gid >> 6) & 31, sb = gid >> 11;
+  if (sb < 4 || sb > 252) return;  // every result a normal bf16: 0.125 x 2^(sb-127) .. 7.5 x 2^(sb-127)
+  const float scale = __builtin_bit_cast(float, sb << 23);
+  const unsigned want = wire_dequantize(code, sb, WireFormat::Mxfp6), marker = sb << 7;  // code 0x08 is 1.0
+  u32x6 c;
+  for (int i = 0; i < 6; ++i) c[i] = 0;
+  for (unsigned j = 0; j < 32; ++j) put_code(c, j, j == pos ? code : 0x08u);
+  const u32x16 b = __builtin_bit_cast(u32x16, __builtin_amdgcn_cvt_scalef32_pk32_bf16_fp6(c, scale));
+  const u32x32 f = __builtin_bit_cast(u32x32, __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(c, scale));
+  unsigned diffb = 0, difff = 0;  // or of the differences: one compare at the end
+  for (unsigned j = 0; j < 32; ++j) {
+    const unsigned w = j == pos ? want : marker;
+    diffb |= ((b[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) ^ w;
+    difff |= f[j] ^ (w << 16);
+  }
+  const bool okb = diffb == 0, okf = difff == 0;
+  atomicAdd(&o->wtotal, 1ull);
+  if (!okb) atomicAdd(&o->wbad[0], 1ull);
+  if (!okf) atomicAdd(&o->wbad[1], 1ull);
+  if (!okb || !okf) {
+    const unsigned n = atomicAdd(&o->wnex, 1u);
+    if (n < 8) { o->wex[n][0] = code | pos << 8; o->wex[n][1] = sb; o->wex[n][2] = (b[pos >> 1] >> (16 * (pos & 1))) & 0xFFFFu; o->wex[n][3] = want; }
+  }
+}
 
 struct Out {
   unsigned long long bad[8];  // [fmt*4 + mode*2 + subnormal]
@@ -121,5 +203,23 @@ int main() {
     for (unsigned n = 0; n < (h.wnex[fi] < 8 ? h.wnex[fi] : 8); ++n)
       printf("    code=%02x sb=%u got=%08x want=%08x\n", h.wex[fi][n][0], h.wex[fi][n][1], h.wex[fi][n][2], h.wex[fi][n][3]);
   }
+  Out6* d6;
+  CK(hipMalloc(&d6, sizeof(Out6)));
+  CK(hipMemset(d6, 0, sizeof(Out6)));
+  narrow6_probe<<<(65536 * 256) / 256, 256>>>(d6);
+  widen6_probe<<<(64 * 32 * 256) / 256, 256>>>(d6);
+  CK(hipDeviceSynchronize());
+  Out6 h6;
+  CK(hipMemcpy(&h6, d6, sizeof(Out6), hipMemcpyDeviceToHost));
+  printf("narrow mxfp6 (pk32_fp6_bf16, value at a varying element, zeros elsewhere): %llu in-contract inputs\n", h6.ntotal);
+  for (int m = 0; m < 2; ++m) printf("  %-26s mismatches %llu\n", mode[m], h6.nbad[m]);
+  for (unsigned n = 0; n < (h6.nnex < 8 ? h6.nnex : 8); ++n)
+    printf("    x=%04x sb=%u got=%02x want=%02x\n", h6.nex[n][0], h6.nex[n][1], h6.nex[n][2], h6.nex[n][3]);
+  printf("widen mxfp6 (every code x element position x scale byte 4..252): %llu inputs, mismatches pk32_bf16_fp6 %llu, pk32_f32_fp6 %llu\n",
+         h6.wtotal, h6.wbad[0], h6.wbad[1]);
+  for (unsigned n = 0; n < (h6.wnex < 8 ? h6.wnex : 8); ++n)
+    printf("    code=%02x pos=%u sb=%u got=%04x want=%04x\n", h6.wex[n][0] & 0xFF, h6.wex[n][0] >> 8, h6.wex[n][1], h6.wex[n][2], h6.wex[n][3]);
+  printf("mxfp6 register layout (element j in bits 6j..6j+5, VGPR 0 lowest): %s\n",
+         h6.nbad[0] == 0 && h6.wbad[0] == 0 && h6.wbad[1] == 0 ? "confirmed" : "NOT confirmed");
   return 0;
 }

@@ -4,7 +4,7 @@ mappings) against the two-launch path, the bf16 reduce and the plain copy, in
 one process and one window.
 
 For each shape (32 MiB x 32 ops, 1 GiB x 1; payload bytes), format (mxfp8,
-mxfp4), fan-in (2, 4, 8) and access form (non-temporal, cross-GPU coherent on
+mxfp6, mxfp4; --formats picks), fan-in (2, 4, 8) and access form (non-temporal, cross-GPU coherent on
 local memory): a sustained warm-up, then 20 rounds in which the candidates take
 turns, each between its own pair of events; the medians.  Candidates:
   split, contiguous  native.wire_reduce, one launch per op, in that lane mapping;
@@ -38,7 +38,7 @@ from copy_checked_bench import alternate, warm  # noqa: E402
 
 MIB = 1 << 20
 SHAPES = [("32MiB x 32", 32 * MIB, 32), ("1GiB x 1", 1024 * MIB, 1)]
-FORMATS = ("mxfp8", "mxfp4")
+FORMATS = ("mxfp8", "mxfp6", "mxfp4")
 FAN_INS = (2, 4, 8)
 NAMES = ("split", "contiguous", "two_pass", "reduce_bf16", "copy")
 
@@ -48,6 +48,7 @@ def main():
     ap.add_argument("--json", help="write the records here")
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warm-seconds", type=float, default=0.3)
+    ap.add_argument("--formats", default=",".join(FORMATS), help="comma-separated subset of " + ", ".join(FORMATS))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("wire_reduce_bench: needs a GPU (no rate is reported without one)")
@@ -61,7 +62,7 @@ def main():
         # bf16 scratch of the two-pass path, also the operands of the bf16 reduce and the copy's source.
         wide = [[torch.empty(nbytes, dtype=torch.uint8, device="cuda") for _ in range(max(FAN_INS))] for _ in range(nops)]
         copy_ops = [(d.data_ptr(), w[0].data_ptr(), nbytes) for d, w in zip(dst, wide)]
-        for fmt in FORMATS:
+        for fmt in args.formats.split(","):
             wb = nat.wire_bytes(nbytes, fmt)
             images = [[torch.empty(wb, dtype=torch.uint8, device="cuda") for _ in range(max(FAN_INS))] for _ in range(nops)]
             for i, (ims, ws) in enumerate(zip(images, wide)):

@@ -270,13 +270,14 @@ def words_to_bytes(w: torch.Tensor) -> torch.Tensor:
 # Per format: stored mantissa bits, exponent of the smallest normal, the
 # maximum as (significand, exponent), the sign's bit and a block's element bytes.
 WIRE_FORMATS = {"mxfp8": dict(mbits=3, emin=-6, top=1.75, emax=8, sign=7, block_bytes=32),
+                "mxfp6": dict(mbits=3, emin=0, top=1.875, emax=2, sign=5, block_bytes=24),
                 "mxfp4": dict(mbits=1, emin=0, top=1.5, emax=2, sign=3, block_bytes=16)}
 WIRE_TILE_BLOCKS = 128
 
 
 def wire_pack_(dst: torch.Tensor, src: torch.Tensor, fmt: str, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """The bytes of ``src`` read as bf16 (a multiple of 64 bytes) -> their
-    'mxfp8' / 'mxfp4' wire image in ``dst`` with the gfx950 pack kernel."""
+    'mxfp8' / 'mxfp6' / 'mxfp4' wire image in ``dst`` with the gfx950 pack kernel."""
     nbytes = _check_tensor(src)
     nat = require_native()
     if _check_tensor(dst) < nat.wire_bytes(nbytes, fmt):
@@ -342,14 +343,19 @@ def _wire_quantize(words: torch.Tensor, fmt: str):
 
 def reference_wire_pack(words: torch.Tensor, fmt: str) -> torch.Tensor:
     """The wire image (uint8) of the bf16 payload ``words`` (int64 words, 16
-    per block): per tile of up to 128 blocks the element bytes, the scale
-    bytes and zeros up to a multiple of 16."""
+    per block): per tile of up to 128 blocks the element bytes (element j in
+    bits bj.. of its block, little-endian) and the scale bytes, each section
+    followed by zeros up to a multiple of 16."""
     sb, code, _ = _wire_quantize(words, fmt)
-    elems = code if fmt == "mxfp8" else code[:, 0::2] | (code[:, 1::2] << 4)
+    if fmt == "mxfp6":  # four 6-bit codes share three bytes
+        v = code[:, 0::4] | (code[:, 1::4] << 6) | (code[:, 2::4] << 12) | (code[:, 3::4] << 18)
+        elems = torch.stack([v & 0xFF, (v >> 8) & 0xFF, v >> 16], dim=2).reshape(-1, 24)
+    else:
+        elems = code if fmt == "mxfp8" else code[:, 0::2] | (code[:, 1::2] << 4)
     parts = []
     for t in range(0, sb.numel(), WIRE_TILE_BLOCKS):
-        tile = torch.cat([elems[t:t + WIRE_TILE_BLOCKS].reshape(-1), sb[t:t + WIRE_TILE_BLOCKS]])
-        parts += [tile, torch.zeros(-tile.numel() % 16, dtype=torch.int64)]
+        for section in (elems[t:t + WIRE_TILE_BLOCKS].reshape(-1), sb[t:t + WIRE_TILE_BLOCKS]):
+            parts += [section, torch.zeros(-section.numel() % 16, dtype=torch.int64)]
     return torch.cat(parts).to(torch.uint8)
 
 
@@ -361,12 +367,13 @@ def reference_wire_roundtrip(words: torch.Tensor, fmt: str) -> torch.Tensor:
     return torch.stack([bits & 0xFF, bits >> 8], dim=1).to(torch.uint8).reshape(-1)
 
 
-def wire_reduce_(dst: torch.Tensor, srcs, fmt: str, *, coherent: bool = False, max_blocks: int = 0,
+def wire_reduce_(dst: torch.Tensor, srcs, fmt: str, *, coherent=False, max_blocks: int = 0,
                  lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
-    """The bytes of ``dst`` as bf16 = the sum of the 1..8 'mxfp8' / 'mxfp4'
-    wire images ``srcs`` in that order, dequantised and added in float32 and
-    rounded once, with the gfx950 wire-reduce kernel (the IPC pull engine's
-    receive under ``--reduce-wire``; stream-ordered)."""
+    """The bytes of ``dst`` as bf16 = the sum of the 1..8 'mxfp8' / 'mxfp6' /
+    'mxfp4' wire images ``srcs`` in that order, dequantised and added in float32
+    and rounded once, with the gfx950 wire-reduce kernel (the IPC pull engine's
+    receive under ``--reduce-wire``; stream-ordered).  ``coherent``: True reads
+    every image in the cross-GPU form, an int is a mask, bit k for source k."""
     nbytes = _check_tensor(dst)
     nat = require_native()
     if any(_check_tensor(s) < nat.wire_bytes(nbytes, fmt) for s in srcs):
