@@ -159,6 +159,14 @@ data
                          round trip through memory.  Flows stay in payload bytes; the image is
                          checked bit for bit.  Same transports and exclusions as --reduce-wire;
                          F is mxfp8 or mxfp4 (mxfp6 sums to bf16 only)
+      --reduce-own FORMAT  wire (default) | bf16, with --reduce bf16 --reduce-wire F: what operand 0
+                         of a receiver's sum is.  bf16: the receiver's own shard as a real rank
+                         holds it, bf16 that was never quantised (8 KiB per tile read, not the
+                         image's 4.2 / 3.2 / 2.2 KiB); only what arrives is dequantised.  Still
+                         one launch: the own shard begins the f32 chains, the incoming images
+                         follow, one rounding.  Peers still pull this rank's image.  Works
+                         with --reduce-out wire (mxfp8, mxfp4).  Same transports and
+                         exclusions as --reduce-wire
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -310,7 +318,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
                                     "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load", "--stream-sizes",
-                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire", "--reduce-wire", "--reduce-out"};
+                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire", "--reduce-wire", "--reduce-out", "--reduce-own"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -437,6 +445,14 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
         return false;
       }
       cfg->run.reduce_out = v == "wire" ? ReduceOut::Wire : ReduceOut::Bf16;
+    } else if (a == "--reduce-own") {
+      const std::string v = next();
+      if (v != "bf16" && v != "wire") {
+        std::fprintf(stderr, "p2p_matrix: --reduce-own '%s': bf16 or wire\n", v.c_str());
+        *exit_code = 1;
+        return false;
+      }
+      cfg->run.reduce_own = v == "bf16" ? ReduceOwn::Bf16 : ReduceOwn::Wire;
     } else if (a == "--load") {
       const std::string v = next();
       std::string why;
@@ -604,6 +620,16 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       *exit_code = 1;
       return false;
     }
+  }
+  // --reduce-own bf16: operand 0 of a --reduce-wire sum, so it needs that
+  // option; everything else that option refuses is refused below under its
+  // own name (and mxfp6 with --reduce-out wire above).
+  if (cfg->run.reduce_own == ReduceOwn::Bf16 &&
+      (cfg->run.reduce != ReduceType::Bf16 || cfg->run.reduce_wire == WireFormat::Off)) {
+    std::fprintf(stderr, "p2p_matrix: --reduce-own bf16 needs --reduce bf16 --reduce-wire FORMAT: it says what operand 0 of "
+                         "that sum of wire images is (the receiver's unquantised shard)\n");
+    *exit_code = 1;
+    return false;
   }
   // --reduce-wire: the sum of --reduce bf16 over operands that arrive as wire
   // images; only where a data plane can do both at once (the pull engine's
@@ -1197,10 +1223,12 @@ int run_app(const AppConfig& cfg, Bootstrap& boot, FILE* out, AppResult* result)
     int most_iters = std::max(cfg.run.iters, cfg.run.warmup);
     if (cfg.iters_auto)
       for (size_t b : cfg.sizes) most_iters = std::max(most_iters, auto_iters(b, cfg.target_bytes));
-    run_cfg.run.gens = verify_generations(*t, boot, max_bytes, slots, most_iters);
+    run_cfg.run.gens = verify_generations(*t, boot, max_bytes, slots, most_iters, cfg.run.reduce_own == ReduceOwn::Bf16);
   }
   if (const char* rc = std::getenv("P2P_RECHUNK")) run_cfg.run.rechunk = std::atoi(rc) != 0;
-  Buffers bufs(*t, max_bytes, slots * run_cfg.run.gens, slot_stride_bytes(max_bytes) * static_cast<size_t>(run_cfg.run.gens));
+  // --reduce-own bf16: a third arena, one own shard per generation (nothing is allocated without the option).
+  const size_t send_bytes = slot_stride_bytes(max_bytes) * static_cast<size_t>(run_cfg.run.gens);
+  Buffers bufs(*t, max_bytes, slots * run_cfg.run.gens, send_bytes, cfg.run.reduce_own == ReduceOwn::Bf16 ? send_bytes : 0);
 
   // Connection warm-up outside any timed cell (the reference pays lazy p2p
   // connection setup inside its first cells; --reference keeps that).

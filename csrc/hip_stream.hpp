@@ -90,16 +90,21 @@ class GpuTransport : public Transport {
     return checks_.verify_unpacked(p, payload_bytes, seed, fmt, stream_, [this] { sync(); });
   }
 
-  VerifyResult verify_reduced_unpacked(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                       WireFormat fmt) override {
+  void fill_wire_operand(void* p, size_t payload_bytes, uint64_t seed) override {
     before_buffer_work();
-    return checks_.verify_wire_reduced(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); });
+    dev::launch_fill_wire_operand(p, payload_bytes, seed, stream_);
+  }
+
+  VerifyResult verify_reduced_unpacked(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
+                                       WireFormat fmt, bool own_bf16) override {
+    before_buffer_work();
+    return checks_.verify_wire_reduced(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); }, own_bf16);
   }
 
   VerifyResult verify_reduced_packed(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                     WireFormat fmt) override {
+                                     WireFormat fmt, bool own_bf16) override {
     before_buffer_work();
-    return checks_.verify_wire_reduced_packed(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); });
+    return checks_.verify_wire_reduced_packed(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); }, own_bf16);
   }
 
   int mark() override;  // one event per mark on the main stream

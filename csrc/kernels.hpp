@@ -283,6 +283,16 @@ struct WireReduceOp {
   int nsrc = 0;
   const void* src[kMaxWireReduceSrcs] = {};
   uint32_t coherent_mask = 0;
+  // --reduce-own bf16: src[0] is the receiver's own shard, payload_bytes of
+  // bf16 in local memory (bit 0 of coherent_mask clear, a P2P_CHECK), not an
+  // image; it begins the f32 chains unquantised (wire_reduce_op.hpp own_bf16).
+  // A lane loads its 16 own elements as two 16 B non-temporal loads (split: 4
+  // KiB apart, both coalesced; contiguous: its 32 B) with the tile's other
+  // loads and widens them with shifts and masks; the mxfp6 kernel, a block per
+  // lane, reads the wave's 4 KiB coalesced and turns it into rows through the
+  // store stage's LDS slot (wire6_lane.hpp load_block).  OWN is a template
+  // parameter beside the fan-in: the all-image kernels are unchanged.
+  bool own_bf16 = false;
 };
 void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks = 0,
                         WireLanes lanes = WireLanes::Auto);
@@ -290,8 +300,13 @@ void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stre
 // unpacks each per block (4 lanes each), sums them with reduce_op.hpp's
 // functions and compares with p word by word; the totals end in acc[0] like
 // launch_verify's (reset acc first).  Never inside timing.
+// own_bf16: operand 0 (seeds[0]) enters as the raw stream.
 void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint64_t* seeds, int nseeds, WireFormat fmt,
-                                VerifyAccum* acc, hipStream_t stream);
+                                VerifyAccum* acc, hipStream_t stream, bool own_bf16 = false);
+// payload_bytes of bf16: operand stream `seed` (wire_operand_word over the
+// fill's stream) unquantised, the own shard of a --reduce-own bf16 sum; what
+// launch_fill_packed packs.  The fill kernel's geometry.
+void launch_fill_wire_operand(void* p, size_t payload_bytes, uint64_t seed, hipStream_t stream);
 
 // ---- the same hop with a requantised output (wire_reduce_pack.hip; --reduce-out wire) ----
 // launch_wire_reduce whose op.dst receives wire_bytes(payload_bytes, fmt)
@@ -317,7 +332,7 @@ void launch_wire_reduce_packed(const WireReduceOp& op, WireFormat fmt, hipStream
 // the lowest byte offset in the image of either; the checksum sums the code
 // words and the scale bytes; the padding is not read.
 void launch_verify_wire_reduced_packed(const void* image, size_t payload_bytes, const uint64_t* seeds, int nseeds,
-                                       WireFormat fmt, VerifyAccum* acc, hipStream_t stream);
+                                       WireFormat fmt, VerifyAccum* acc, hipStream_t stream, bool own_bf16 = false);
 
 // ---- device-initiated ping-pong (pingpong.hip) ----
 // One wave per role.  The leader writes message i (payload words = base+i+1,

@@ -113,7 +113,8 @@ class Session {
   std::string run(const std::string& mode, const std::string& dir, size_t bytes, int iters, int warmup,
                   const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
                   int diagnose, bool inline_check, const std::string& load, const std::string& reduce,
-                  const std::string& wire, const std::string& reduce_wire, const std::string& reduce_out) {
+                  const std::string& wire, const std::string& reduce_wire, const std::string& reduce_out,
+                  const std::string& reduce_own) {
     LoadSpec load_spec;
     std::string why;
     P2P_CHECK(load.empty() || parse_load_spec(load, &load_spec, &why), "load '" + load + "': " + why);
@@ -158,12 +159,19 @@ class Session {
     P2P_CHECK(reduce_out != "wire" || cfg.reduce_wire != WireFormat::Mxfp6,
               "reduce_out='wire' with reduce_wire='mxfp6': 6-bit images are summed to bf16 only (mxfp8 and mxfp4 requantise)");
     if (reduce_out == "wire") cfg.reduce_out = ReduceOut::Wire;
+    // reduce_own="bf16": operand 0 of the sum is the receiver's unquantised shard (RunConfig::reduce_own).
+    P2P_CHECK(reduce_own.empty() || reduce_own == "bf16" || reduce_own == "wire", "reduce_own '" + reduce_own + "': bf16 or wire");
+    P2P_CHECK(reduce_own != "bf16" || cfg.reduce_wire != WireFormat::Off,
+              "reduce_own='bf16' needs reduce='bf16' and reduce_wire (it says what operand 0 of that sum of wire images is)");
+    const bool own_shard = reduce_own == "bf16";
+    if (own_shard) cfg.reduce_own = ReduceOwn::Bf16;
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
-    cfg.gens = verify ? verify_generations(*t_, *boot_, bytes, slots, std::max(iters, warmup)) : 1;
+    cfg.gens = verify ? verify_generations(*t_, *boot_, bytes, slots, std::max(iters, warmup), own_shard) : 1;
     if (const char* rc = std::getenv("P2P_RECHUNK")) cfg.rechunk = std::atoi(rc) != 0;
-    Buffers bufs(*t_, bytes, slots * cfg.gens, slot_stride_bytes(bytes) * static_cast<size_t>(cfg.gens));
+    const size_t send_bytes = slot_stride_bytes(bytes) * static_cast<size_t>(cfg.gens);
+    Buffers bufs(*t_, bytes, slots * cfg.gens, send_bytes, own_shard ? send_bytes : 0);
     if (warm) {
       warm_connections(*t_, *boot_, s, bufs);
       t_->refine_op_limits(*boot_);
@@ -516,14 +524,15 @@ py::tuple device_verify_unpacked(uintptr_t ptr, size_t payload_bytes, uint64_t s
 }
 
 // ---- sum of wire images (kernels.hpp WireReduceOp) on raw pointers ----
-void device_wire_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t payload_bytes, const std::string& fmt,
-                        uintptr_t stream, const py::object& coherent, int max_blocks, const std::string& lanes) {
-  const WireFormat f = wire_format_arg(fmt);
+// own_bf16: srcs[0] is payload_bytes of bf16, the own shard (WireReduceOp::own_bf16).
+dev::WireReduceOp wire_reduce_op_arg(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t payload_bytes,
+                                     const py::object& coherent, bool own_bf16, const char* who) {
   if (srcs.empty() || srcs.size() > static_cast<size_t>(kMaxWireReduceSrcs))
-    throw py::value_error("wire_reduce: 1..8 source images");
+    throw py::value_error(std::string(who) + ": 1..8 source images");
   dev::WireReduceOp op;
   op.dst = reinterpret_cast<void*>(dst);
   op.payload_bytes = wire_payload_arg(payload_bytes);
+  op.own_bf16 = own_bf16;
   for (uintptr_t s : srcs) op.src[op.nsrc++] = reinterpret_cast<const void*>(s);
   // A bool is every source; an int is WireReduceOp::coherent_mask, bit k for source k.
   const uint32_t all = (1u << op.nsrc) - 1u;
@@ -531,14 +540,21 @@ void device_wire_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_
     op.coherent_mask = coherent.cast<bool>() ? all : 0u;
   } else {
     const uint64_t mask = coherent.cast<uint64_t>();
-    if (mask & ~static_cast<uint64_t>(all)) throw py::value_error("wire_reduce: the coherent mask names a source the op does not have");
+    if (mask & ~static_cast<uint64_t>(all)) throw py::value_error(std::string(who) + ": the coherent mask names a source the op does not have");
     op.coherent_mask = static_cast<uint32_t>(mask);
   }
+  return op;
+}
+
+void device_wire_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t payload_bytes, const std::string& fmt,
+                        uintptr_t stream, const py::object& coherent, int max_blocks, const std::string& lanes, bool own_bf16) {
+  const WireFormat f = wire_format_arg(fmt);
+  const dev::WireReduceOp op = wire_reduce_op_arg(dst, srcs, payload_bytes, coherent, own_bf16, "wire_reduce");
   dev::launch_wire_reduce(op, f, as_stream(stream), max_blocks, wire_lanes_arg(lanes));
 }
 
 py::tuple device_verify_wire_reduced(uintptr_t ptr, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                     const std::string& fmt, uintptr_t stream) {
+                                     const std::string& fmt, uintptr_t stream, bool own_bf16) {
   const WireFormat f = wire_format_arg(fmt);
   wire_payload_arg(payload_bytes);
   DeviceChecks& c = checks_for_current_device();
@@ -546,27 +562,22 @@ py::tuple device_verify_wire_reduced(uintptr_t ptr, size_t payload_bytes, const 
   VerifyResult r;
   {
     py::gil_scoped_release nogil;
-    r = c.verify_wire_reduced(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st));
+    r = c.verify_wire_reduced(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st), own_bf16);
   }
   return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
 
 // ---- the same sum, requantised (kernels.hpp launch_wire_reduce_packed) ----
 void device_wire_reduce_packed(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t payload_bytes, const std::string& fmt,
-                               uintptr_t stream, bool coherent, int max_blocks, const std::string& lanes) {
+                               uintptr_t stream, const py::object& coherent, int max_blocks, const std::string& lanes,
+                               bool own_bf16) {
   const WireFormat f = wire_format_arg(fmt);
-  if (srcs.empty() || srcs.size() > static_cast<size_t>(kMaxWireReduceSrcs))
-    throw py::value_error("wire_reduce_packed: 1..8 source images");
-  dev::WireReduceOp op;
-  op.dst = reinterpret_cast<void*>(dst);
-  op.payload_bytes = wire_payload_arg(payload_bytes);
-  for (uintptr_t s : srcs) op.src[op.nsrc++] = reinterpret_cast<const void*>(s);
-  if (coherent) op.coherent_mask = (1u << op.nsrc) - 1u;
+  const dev::WireReduceOp op = wire_reduce_op_arg(dst, srcs, payload_bytes, coherent, own_bf16, "wire_reduce_packed");
   dev::launch_wire_reduce_packed(op, f, as_stream(stream), max_blocks, wire_lanes_arg(lanes));
 }
 
 py::tuple device_verify_wire_reduced_packed(uintptr_t ptr, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                            const std::string& fmt, uintptr_t stream) {
+                                            const std::string& fmt, uintptr_t stream, bool own_bf16) {
   const WireFormat f = wire_format_arg(fmt);
   wire_payload_arg(payload_bytes);
   DeviceChecks& c = checks_for_current_device();
@@ -574,7 +585,7 @@ py::tuple device_verify_wire_reduced_packed(uintptr_t ptr, size_t payload_bytes,
   VerifyResult r;
   {
     py::gil_scoped_release nogil;
-    r = c.verify_wire_reduced_packed(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st));
+    r = c.verify_wire_reduced_packed(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st), own_bf16);
   }
   return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
@@ -1074,7 +1085,7 @@ PYBIND11_MODULE(_p2pcore, m) {
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
            py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
            py::arg("inline_check") = false, py::arg("load") = "", py::arg("reduce") = "", py::arg("wire") = "",
-           py::arg("reduce_wire") = "", py::arg("reduce_out") = "", py::call_guard<NativeCall, py::gil_scoped_release>())
+           py::arg("reduce_wire") = "", py::arg("reduce_out") = "", py::arg("reduce_own") = "", py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("device_latency", &Session::device_latency, py::arg("bytes") = 8, py::arg("iters") = 1000,
@@ -1335,51 +1346,61 @@ PYBIND11_MODULE(_p2pcore, m) {
       }, py::arg("wire"), py::arg("payload_bytes"), py::arg("fmt"), "CPU unpack, bit-compatible with the unpack kernel.");
   m.def("wire_reduce", &device_wire_reduce, py::arg("dst"), py::arg("srcs"), py::arg("payload_bytes"), py::arg("fmt"),
         py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0, py::arg("lanes") = "auto",
+        py::arg("own_bf16") = false,
         "The IPC transport's gfx950 wire-reduce kernel: dst = payload_bytes of bf16, the f32 sum of the 1..8 'mxfp8', 'mxfp6' or "
         "'mxfp4' wire images at srcs in that order, rounded once (coherent: True reads every image in the cross-GPU form, an int is a mask, bit k for source k; lanes: "
-        "'auto', 'contiguous' or 'split' lane mapping).");
+        "'auto', 'contiguous' or 'split' lane mapping; own_bf16: srcs[0] is payload_bytes of bf16 in local memory, the receiver's "
+        "own shard, which enters the sum unquantised).");
+  m.def("fill_wire_operand", [](uintptr_t ptr, size_t payload_bytes, uint64_t seed, uintptr_t stream) {
+        dev::launch_fill_wire_operand(reinterpret_cast<void*>(ptr), wire_payload_arg(payload_bytes), seed, as_stream(stream));
+      }, py::arg("ptr"), py::arg("payload_bytes"), py::arg("seed"), py::arg("stream") = 0,
+      "Fills payload_bytes at ptr with bf16 operand stream `seed`, unquantised: the own shard of an own_bf16 sum.");
   m.def("verify_wire_reduced", &device_verify_wire_reduced, py::arg("ptr"), py::arg("payload_bytes"), py::arg("seeds"),
-        py::arg("fmt"), py::arg("stream") = 0,
+        py::arg("fmt"), py::arg("stream") = 0, py::arg("own_bf16") = false,
         "Compares the buffer with the sum of the operand streams `seeds` (operand order), each packed and unpacked: (wrong "
         "32-bit words, checksum, first bad byte offset or 2**64-1).");
-  m.def("host_wire_reduce", [](const std::vector<py::bytes>& images, size_t payload_bytes, const std::string& fmt) {
+  m.def("host_wire_reduce", [](const std::vector<py::bytes>& images, size_t payload_bytes, const std::string& fmt, bool own_bf16) {
         const WireFormat f = wire_format_arg(fmt);
         if (images.empty() || images.size() > static_cast<size_t>(kMaxWireReduceSrcs))
           throw py::value_error("host_wire_reduce: 1..8 images");
         std::vector<std::string> data(images.begin(), images.end());
         std::vector<const void*> p;
         for (const std::string& d : data) {
-          if (d.size() != wire_bytes(wire_payload_arg(payload_bytes), f)) throw py::value_error("host_wire_reduce: wire_bytes() per image");
+          const size_t want = own_bf16 && p.empty() ? wire_payload_arg(payload_bytes) : wire_bytes(wire_payload_arg(payload_bytes), f);
+          if (d.size() != want) throw py::value_error("host_wire_reduce: wire_bytes() per image (own_bf16: payload_bytes for the first)");
           p.push_back(d.data());
         }
         std::string out(payload_bytes, '\0');
-        host_wire_reduce(&out[0], p.data(), static_cast<int>(p.size()), payload_bytes, f);
+        host_wire_reduce(&out[0], p.data(), static_cast<int>(p.size()), payload_bytes, f, own_bf16);
         return py::bytes(out);
-      }, py::arg("images"), py::arg("payload_bytes"), py::arg("fmt"),
+      }, py::arg("images"), py::arg("payload_bytes"), py::arg("fmt"), py::arg("own_bf16") = false,
       "CPU sum of wire images in order as bf16 bytes, bit-compatible with the wire-reduce kernel.");
   m.def("wire_reduce_packed", &device_wire_reduce_packed, py::arg("dst"), py::arg("srcs"), py::arg("payload_bytes"),
         py::arg("fmt"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0, py::arg("lanes") = "auto",
+        py::arg("own_bf16") = false,
         "The gfx950 wire-reduce-pack kernel: dst = wire_bytes(payload_bytes, fmt) bytes, the wire image in fmt of the bf16 sum "
-        "wire_reduce gives for the 1..8 images at srcs, in one launch (coherent, lanes: as wire_reduce).");
+        "wire_reduce gives for the 1..8 images at srcs, in one launch (coherent: True reads every image in the cross-GPU form; an int, 1 included, is a mask with bit k for "
+        "source k, as in wire_reduce, where it used to mean every source; lanes and own_bf16: as wire_reduce).");
   m.def("verify_wire_reduced_packed", &device_verify_wire_reduced_packed, py::arg("ptr"), py::arg("payload_bytes"),
-        py::arg("seeds"), py::arg("fmt"), py::arg("stream") = 0,
+        py::arg("seeds"), py::arg("fmt"), py::arg("stream") = 0, py::arg("own_bf16") = false,
         "Compares the image with the packed sum of the operand streams `seeds`: (wrong 32-bit code words + wrong scale bytes, "
         "checksum of code words and scale bytes, first bad byte offset in the image or 2**64-1).");
-  m.def("host_wire_reduce_packed", [](const std::vector<py::bytes>& images, size_t payload_bytes, const std::string& fmt) {
+  m.def("host_wire_reduce_packed", [](const std::vector<py::bytes>& images, size_t payload_bytes, const std::string& fmt,
+                                      bool own_bf16) {
         const WireFormat f = wire_format_arg(fmt);
         if (images.empty() || images.size() > static_cast<size_t>(kMaxWireReduceSrcs))
           throw py::value_error("host_wire_reduce_packed: 1..8 images");
         std::vector<std::string> data(images.begin(), images.end());
         std::vector<const void*> p;
         for (const std::string& d : data) {
-          if (d.size() != wire_bytes(wire_payload_arg(payload_bytes), f))
-            throw py::value_error("host_wire_reduce_packed: wire_bytes() per image");
+          if (d.size() != (own_bf16 && p.empty() ? wire_payload_arg(payload_bytes) : wire_bytes(wire_payload_arg(payload_bytes), f)))
+            throw py::value_error("host_wire_reduce_packed: wire_bytes() per image (own_bf16: payload_bytes for the first)");
           p.push_back(d.data());
         }
         std::string out(wire_bytes(payload_bytes, f), '\0');
-        host_wire_reduce_packed(&out[0], p.data(), static_cast<int>(p.size()), payload_bytes, f);
+        host_wire_reduce_packed(&out[0], p.data(), static_cast<int>(p.size()), payload_bytes, f, own_bf16);
         return py::bytes(out);
-      }, py::arg("images"), py::arg("payload_bytes"), py::arg("fmt"),
+      }, py::arg("images"), py::arg("payload_bytes"), py::arg("fmt"), py::arg("own_bf16") = false,
       "CPU sum of wire images, packed again: the image the wire-reduce-pack kernel stores, bit for bit.");
   m.attr("MAX_SIGNALS") = dev::kMaxSignals;
   m.def("signal", [](const FlagList& posts, const FlagList& waits, uintptr_t status_ptr, uint64_t timeout_ticks,

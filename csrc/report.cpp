@@ -230,6 +230,7 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
   if (rec.cfg.reduce_wire != WireFormat::Off)
     head.insert(head.size() - 1, strfmt(" reduce-wire=%s", wire_format_name(rec.cfg.reduce_wire)));
   if (rec.cfg.reduce_out == ReduceOut::Wire) head.insert(head.size() - 1, " reduce-out=wire");
+  if (rec.cfg.reduce_own == ReduceOwn::Bf16) head.insert(head.size() - 1, " reduce-own=bf16");
   std::fprintf(out, "\n== %s ==\n", head.c_str());
   bool blank_diag = rec.mode != Mode::Self && n > 1;
   auto gbs = flow_matrix_gbs(rec, n);
@@ -271,14 +272,18 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
                  static_cast<unsigned long long>(timed));
   if (rec.cfg.reduce_wire != WireFormat::Off)
     std::fprintf(out,
-                 "  reduce: %s over %s images, every receiver sums its own image and its incoming ones in one launch; "
+                 "  reduce: %s over %s images, every receiver sums its own %s and its incoming ones in one launch; "
                  "%llu wire bytes per %llu-byte bf16 message, rates are payload bytes\n",
                  reduce_type_name(rec.cfg.reduce), wire_format_name(rec.cfg.reduce_wire),
+                 rec.cfg.reduce_own == ReduceOwn::Bf16 ? "bf16 shard" : "image",
                  static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)),
                  static_cast<unsigned long long>(rec.cfg.bytes));
   else if (rec.cfg.reduce != ReduceType::Off)
     std::fprintf(out, "  reduce: %s, every receiver sums its own shard and its incoming messages in one launch\n",
                  reduce_type_name(rec.cfg.reduce));
+  if (rec.cfg.reduce_own == ReduceOwn::Bf16)
+    std::fprintf(out, "  reduce-own: operand 0 is the receiver's own shard in bf16 (%llu bytes, never quantised), not its image\n",
+                 static_cast<unsigned long long>(rec.cfg.bytes));
   if (rec.cfg.reduce_out == ReduceOut::Wire)
     std::fprintf(out, "  reduce-out: the sum is requantised in the same launch and stored as a %llu-byte %s image\n",
                  static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)),
@@ -424,6 +429,7 @@ std::string run_to_json(const RunRecord& rec, int n) {
     if (rec.cfg.reduce_out == ReduceOut::Wire)  // --reduce-out wire: what the sum leaves in the slot
       o << ",\"out\":{\"format\":\"" << wire_format_name(rec.cfg.reduce_wire)
         << "\",\"bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire) << "}";
+    if (rec.cfg.reduce_own == ReduceOwn::Bf16) o << ",\"own\":\"bf16\"";  // --reduce-own bf16: operand 0 is unquantised
     o << "}";
   }
   if (rec.cfg.wire != WireFormat::Off)  // present only when the option is on

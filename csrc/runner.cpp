@@ -35,14 +35,14 @@ namespace detail {
 size_t slot_stride(size_t bytes) { return (std::max<size_t>(bytes, 16) + 4095) / 4096 * 4096; }
 }  // namespace detail
 
-Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes)
+Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes, size_t own_bytes)
     : t_(t), cap_(std::max<size_t>(slot_bytes, 16)), send_cap_(std::max(send_bytes, cap_)), stride_(slot_stride(cap_)),
-      nslots_(std::max(recv_slots, 1)) {
+      nslots_(std::max(recv_slots, 1)), own_cap_(own_bytes) {
   // One send buffer + one receive arena: check against free HBM up front so a
   // 288 GB sweep fails with an explanation instead of a hipMalloc error mid-run.
   size_t free_b = 0, total_b = 0;
   const double arena = static_cast<double>(stride_) * static_cast<double>(nslots_);
-  const double need = static_cast<double>(send_cap_) + arena;
+  const double need = static_cast<double>(send_cap_) + arena + static_cast<double>(own_cap_);
   if (t_.mem_info(&free_b, &total_b) && need > 0.98 * static_cast<double>(free_b))
     P2P_FATAL(strfmt("buffers need %.2f GiB (send %s + %d receive slots of %s) but only %.2f of %.2f GiB are free on "
                      "this GPU; use a smaller --size/--sizes maximum or a mode with fewer concurrent peers",
@@ -50,6 +50,7 @@ Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_by
                      static_cast<double>(free_b) / (1ull << 30), static_cast<double>(total_b) / (1ull << 30)));
   send_ = t_.alloc(send_cap_);
   recv_ = t_.alloc(stride_ * static_cast<size_t>(nslots_));
+  if (own_cap_) own_ = t_.alloc(own_cap_);  // local operands only: not part of the registered set
   Transport::BufferSet set;
   set.send = send_;
   set.send_bytes = send_cap_;
@@ -66,6 +67,7 @@ Buffers::~Buffers() {
   // on, so the first error is the one that surfaces.
   try {
     t_.unregister_buffers(send_);
+    if (own_) t_.release(own_);
     if (recv_) t_.release(recv_);
     if (send_) t_.release(send_);
   } catch (const std::exception& e) {
@@ -137,7 +139,7 @@ std::vector<Transport::GroupFlow> group_flow_list(const Phase& phase) {
 
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen,
                           const InlineRecords* check, ReduceType reduce, WireFormat wire, WireFormat reduce_wire,
-                          ReduceOut reduce_out) {
+                          ReduceOut reduce_out, ReduceOwn reduce_own) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const std::vector<int> rs = remote_slots(phase, t.rank());
   const int base = gen * std::max(1, phase.max_recv_slots());
@@ -155,10 +157,14 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
   const WireFormat image = wire != WireFormat::Off ? wire : reduce_wire;
   const size_t sent = image == WireFormat::Off ? bytes : static_cast<size_t>(wire_bytes(bytes, image));
   for (size_t j = 0; j < ops.send_to.size(); ++j) t.send_to_slot(bufs.send_at(off), sent, ops.send_to[j], base + rs[j]);
+  // The receiver's own operand: its image in the send region, or its bf16 shard in the own arena.
+  const bool own_bf16 = reduce_own == ReduceOwn::Bf16;
+  P2P_CHECK(!own_bf16 || off + bytes <= bufs.own_capacity(), "reduce_own bf16: the buffers hold no own shard for this generation");
+  const void* own = own_bf16 ? bufs.own_at(off) : bufs.send_at(off);
   if (reduce_wire != WireFormat::Off && reduce_out == ReduceOut::Wire && !ops.recv_from.empty())
-    t.reduce_packed_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce_wire);
+    t.reduce_packed_from(bufs.recv_buf(base), bytes, own, ops.recv_from, off, reduce_wire, own_bf16);
   else if (reduce_wire != WireFormat::Off && !ops.recv_from.empty())
-    t.reduce_unpacked_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce_wire);
+    t.reduce_unpacked_from(bufs.recv_buf(base), bytes, own, ops.recv_from, off, reduce_wire, own_bf16);
   else if (reduce != ReduceType::Off && !ops.recv_from.empty())
     t.reduce_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce);
   for (size_t i = 0; reduce == ReduceType::Off && i < ops.recv_from.size(); ++i) {
@@ -192,9 +198,9 @@ size_t shared_free_budget(Transport& t, Bootstrap& boot, size_t fallback, size_t
   return budget;
 }
 
-int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters) {
-  // One generation = a send region + `slots` receive slots.
-  const size_t per_gen = slot_stride(max_bytes) * static_cast<size_t>(std::max(1, slots) + 1);
+int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters, bool own_shard) {
+  // One generation = a send region + `slots` receive slots (+ a region of the own arena).
+  const size_t per_gen = slot_stride(max_bytes) * static_cast<size_t>(std::max(1, slots) + 1 + (own_shard ? 1 : 0));
   size_t budget = shared_free_budget(t, boot, size_t{256} << 20, size_t{32} << 30);
   if (const char* b = std::getenv("P2P_VERIFY_BUDGET")) budget = parse_size(b);
   long g = std::max(1, iters);
@@ -238,6 +244,12 @@ void prepare_payload(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
     for (int g = 0; g < gens && !(ops.send_to.empty() && ops.recv_from.empty()); ++g)
       t.fill_packed(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
                     generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.reduce_wire);
+    // --reduce-own bf16: a receiver's operand 0 is the same stream unquantised, in the own arena.
+    for (int g = 0; g < gens && cfg.reduce_own == ReduceOwn::Bf16 && !ops.recv_from.empty(); ++g) {
+      const size_t off = slot_stride(cfg.bytes) * static_cast<size_t>(g);
+      P2P_CHECK(off + cfg.bytes <= bufs.own_capacity(), "reduce_own bf16: the buffers hold no own shard for this generation");
+      t.fill_wire_operand(bufs.own_at(off), cfg.bytes, generation_seed(t.rank(), cfg.bytes, cfg.salt, g));
+    }
   } else if (cfg.reduce != ReduceType::Off) {
     for (int g = 0; g < gens && !(ops.send_to.empty() && ops.recv_from.empty()); ++g)
       t.fill_operand(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
@@ -267,10 +279,11 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
     for (int g = 0; g < gens && !ops.recv_from.empty(); ++g) {
       std::vector<uint64_t> seeds{generation_seed(t.rank(), cfg.bytes, cfg.salt, g)};
       for (int peer : ops.recv_from) seeds.push_back(generation_seed(peer, cfg.bytes, cfg.salt, g));
+      const bool own_bf16 = cfg.reduce_own == ReduceOwn::Bf16;
       const VerifyResult v = cfg.reduce_out == ReduceOut::Wire
-                                 ? t.verify_reduced_packed(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire)
+                                 ? t.verify_reduced_packed(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire, own_bf16)
                                  : cfg.reduce_wire != WireFormat::Off
-                                 ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire)
+                                 ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire, own_bf16)
                                  : t.verify_reduced(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce);
       bad += v.mismatches;
       if (per_job)
@@ -447,7 +460,7 @@ void rechunk_until_warmup_verifies(Transport& t, Bootstrap& boot, const Phase& p
     }
     boot.barrier();
     if (active) {
-      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out);
+      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own);
       t.sync();
     }
     bad = boot.allreduce_sum_u64(local_mismatches());
@@ -637,6 +650,8 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   }
   P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Off,
             "reduce_out wire: only with reduce_wire (the image's format is the operands')");
+  P2P_CHECK(cfg.reduce_own == ReduceOwn::Wire || cfg.reduce_wire != WireFormat::Off,
+            "reduce_own bf16: only with reduce_wire (it says what operand 0 of that sum is)");
   P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Mxfp6,
             "reduce_out wire: not with reduce_wire mxfp6 (6-bit images are summed to bf16 only)");
   if (cfg.wire != WireFormat::Off) {
@@ -666,7 +681,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   const double hooked0 = now_seconds();
   if (cfg.before_timing) cfg.before_timing();
   if (active) {
-    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out);
+    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own);
     t.sync();
   }
   if (cfg.verify && cfg.warmup > 0) {
@@ -710,7 +725,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   auto post = [&](int i) {
     if (skip_some) t.set_discard(i % 2 == 0);
     const InlineRecords rec{static_cast<size_t>(i) * nrecv, cfg.salt};
-    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out);
+    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own);
   };
 
   double my_seconds = 0;

@@ -34,6 +34,7 @@ const char* timing_name(Timing t);
 Timing parse_timing(const std::string& s);
 
 enum class ReduceOut : int { Bf16 = 0, Wire = 1 };
+enum class ReduceOwn : int { Wire = 0, Bf16 = 1 };
 
 struct RunConfig {
   size_t bytes = 32u << 20;  // reference: msg_size = 32 MiB (p2p_matrix.cc:124)
@@ -106,6 +107,14 @@ struct RunConfig {
   // packed sum of the operand streams.  Flows are still timed and reported in
   // payload bytes.  Wire needs reduce_wire.
   ReduceOut reduce_out = ReduceOut::Bf16;
+  // What operand 0 of a reduce_wire sum is (--reduce-own).  Wire: the
+  // receiver's own image, as above.  Bf16: the receiver's own shard as a real
+  // rank holds it, bytes of bf16 that were never quantised, read from the own
+  // arena of the buffers (Buffers::own_at; the send region still holds the
+  // image the peers pull); only what arrives is dequantised.  Same stream and
+  // seed as the image, so the checks' seeds do not change, only operand 0's
+  // round trip is skipped.  Bf16 needs reduce_wire.
+  ReduceOwn reduce_own = ReduceOwn::Wire;
   // Hooks around what a phase measures (--load brackets it with a background
   // load): run_phase calls them on every rank of a non-idle phase, in both
   // timings.  before_timing: after the payload and the poison are posted,
@@ -214,13 +223,17 @@ struct PhaseResult {
 class Buffers {
  public:
   // `slot_bytes` per receive slot; the send buffer holds `send_bytes`
-  // (default: one message).
-  Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes = 0);
+  // (default: one message).  own_bytes > 0 adds a third arena of that size
+  // (RunConfig::reduce_own = Bf16: one slot_stride per generation), local
+  // memory that no peer reads: it is not registered.
+  Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes = 0, size_t own_bytes = 0);
   ~Buffers();
   Buffers(const Buffers&) = delete;
   Buffers& operator=(const Buffers&) = delete;
   void* send_buf() const { return send_; }
   void* send_at(size_t offset) const { return static_cast<char*>(send_) + offset; }
+  void* own_at(size_t offset) const { return own_ ? static_cast<char*>(own_) + offset : nullptr; }
+  size_t own_capacity() const { return own_cap_; }
   void* recv_buf(int slot) const;
   void* recv_base() const { return recv_; }
   size_t capacity() const { return cap_; }          // bytes per receive slot
@@ -236,6 +249,8 @@ class Buffers {
   int nslots_;
   void* send_ = nullptr;
   void* recv_ = nullptr;
+  size_t own_cap_ = 0;
+  void* own_ = nullptr;
 };
 
 // Receive slot on `peer` that holds messages from `me` in `phase` (position
@@ -260,18 +275,20 @@ struct InlineRecords {
 // slot gen * phase.max_recv_slots(), the local operand being send region gen.
 // With `reduce_wire` (and reduce = bf16), sends move the packed image and that
 // one call is Transport::reduce_unpacked_from, or reduce_packed_from with
-// `reduce_out` = Wire.
+// `reduce_out` = Wire; with `reduce_own` = Bf16 its local operand is the
+// generation's region of the own arena, not the send region.
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0,
                           const InlineRecords* check = nullptr, ReduceType reduce = ReduceType::Off,
                           WireFormat wire = WireFormat::Off, WireFormat reduce_wire = WireFormat::Off,
-                          ReduceOut reduce_out = ReduceOut::Bf16);
+                          ReduceOut reduce_out = ReduceOut::Bf16, ReduceOwn reduce_own = ReduceOwn::Wire);
 
 // Receive generations for verified runs of messages up to `max_bytes` with
 // `slots` receive slots per iteration and up to `iters` iterations: as many as
 // P2P_VERIFY_BUDGET bytes of send regions + receive slots allow (default a
 // quarter of free device memory, at most 32 GiB; 256 MiB where the transport
-// cannot tell), agreed by every rank (collective).
-int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters);
+// cannot tell), agreed by every rank (collective).  own_shard: a generation
+// also holds a region of the own arena (RunConfig::reduce_own = Bf16).
+int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters, bool own_shard = false);
 // Collective: a quarter of this rank's GPU's free memory (at most `cap`;
 // `fallback` where the transport cannot tell), divided between the ranks that
 // share the GPU (Transport::device_key).  Every rank drains its stream and

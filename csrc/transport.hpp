@@ -170,11 +170,19 @@ class Transport {
   //   verify_reduced_unpacked  blocking: p against the sum of the operand
   //                            streams `seeds` (operand order), each packed
   //                            and unpacked; a wrong 32-bit word counted once.
+  // own_bf16 (--reduce-own bf16): `local_image` is not an image but the
+  // receiver's own shard, payload_bytes of bf16 in local memory outside the
+  // send region (peers still pull the image from there); it enters the sum
+  // unquantised, and the checks regenerate seeds[0] without the round trip.
+  //   fill_wire_operand        operand stream `seed` as bf16, such a shard.
   virtual bool supports_reduce_wire() const { return false; }
+  virtual void fill_wire_operand(void* /*p*/, size_t /*payload_bytes*/, uint64_t /*seed*/) {}
   virtual void reduce_unpacked_from(void* /*dst*/, size_t /*payload_bytes*/, const void* /*local_image*/,
-                                    const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/) {}
+                                    const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/,
+                                    bool /*own_bf16*/ = false) {}
   virtual VerifyResult verify_reduced_unpacked(const void* /*p*/, size_t /*payload_bytes*/,
-                                               const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/) {
+                                               const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/,
+                                               bool /*own_bf16*/ = false) {
     return {};
   }
   // The same hop with a requantised output (--reduce-out wire): dst receives
@@ -186,9 +194,11 @@ class Transport {
   //                          of the operand streams; a wrong 32-bit word of
   //                          element codes and a wrong scale byte count once.
   virtual void reduce_packed_from(void* /*dst*/, size_t /*payload_bytes*/, const void* /*local_image*/,
-                                  const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/) {}
+                                  const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/,
+                                  bool /*own_bf16*/ = false) {}
   virtual VerifyResult verify_reduced_packed(const void* /*p*/, size_t /*payload_bytes*/,
-                                             const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/) {
+                                             const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/,
+                                             bool /*own_bf16*/ = false) {
     return {};
   }
 

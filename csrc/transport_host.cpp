@@ -189,7 +189,7 @@ VerifyResult host_verify_unpacked(const void* p, size_t n, uint64_t seed, WireFo
 }
 
 // ---- sum of wire images (wire_reduce_op.hpp) ----
-void host_wire_reduce(void* out, const void* const* images, int k, size_t n, WireFormat f) {
+void host_wire_reduce(void* out, const void* const* images, int k, size_t n, WireFormat f, bool own_bf16) {
   check_wire(n, f, "host_wire_reduce");
   P2P_CHECK(k >= 1 && k <= kMaxWireReduceSrcs, "host_wire_reduce: 1..8 images");
   for_each_wire_block(n, f, [&](size_t at, size_t elems, size_t scale) {
@@ -197,7 +197,8 @@ void host_wire_reduce(void* out, const void* const* images, int k, size_t n, Wir
     for (int j = 0; j < k; ++j) {
       const auto* in = static_cast<const uint8_t*>(images[j]);
       uint16_t x[kWireBlockElems];
-      wire_unpack_block(in + elems, in[scale], x, f);
+      if (own_bf16 && j == 0) std::memcpy(x, in + at, sizeof(x));  // the own shard: bf16 as it is
+      else wire_unpack_block(in + elems, in[scale], x, f);
       for (uint32_t i = 0; i < 16; ++i) w[j][i] = x[2 * i] | static_cast<uint32_t>(x[2 * i + 1]) << 16;
     }
     for (uint32_t i = 0; i < 16; ++i) {
@@ -209,7 +210,16 @@ void host_wire_reduce(void* out, const void* const* images, int k, size_t n, Wir
   });
 }
 
-VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f) {
+void host_fill_wire_operand(void* p, size_t n, uint64_t seed) {
+  P2P_CHECK(n % kWireBlockBytes == 0, "host_fill_wire_operand: the payload is a multiple of 64 bytes (blocks of 32 bf16)");
+  for (size_t at = 0; at < n; at += kWireBlockBytes) {
+    uint16_t x[kWireBlockElems];
+    wire_operand_block(seed, at / kWireBlockBytes, x);
+    std::memcpy(static_cast<char*>(p) + at, x, sizeof(x));
+  }
+}
+
+VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f, bool own_bf16) {
   check_wire(n, f, "host_verify_wire_reduced");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "host_verify_wire_reduced: 1..8 operand seeds");
   VerifyResult r;
@@ -227,7 +237,7 @@ VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* s
       for (int j = 0; j < nseeds; ++j) w[j] = x[j][2 * i] | static_cast<uint32_t>(x[j][2 * i + 1]) << 16;
       std::memcpy(&got, static_cast<const char*>(p) + at + 4 * i, 4);
       r.checksum += got;
-      if (got != wire_reduce_word(w, sb, nseeds, f)) {
+      if (got != wire_reduce_word(w, sb, nseeds, f, own_bf16)) {
         if (!r.mismatches) r.first_bad = at + 4 * i;
         ++r.mismatches;
       }
@@ -237,15 +247,16 @@ VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* s
 }
 
 // ---- the same sum, requantised (wire_reduce_op.hpp) ----
-void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f) {
+void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f, bool own_bf16) {
   check_wire(n, f, "host_wire_reduce_packed");
   P2P_CHECK(f != WireFormat::Mxfp6, "host_wire_reduce_packed: mxfp6 images are summed to bf16 only (no requantised output yet)");
   std::vector<char> sum(n);
-  host_wire_reduce(sum.data(), images, k, n, f);
+  host_wire_reduce(sum.data(), images, k, n, f, own_bf16);
   host_wire_pack(out_image, sum.data(), n, f);
 }
 
-VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f) {
+VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f,
+                                             bool own_bf16) {
   check_wire(n, f, "host_verify_wire_reduced_packed");
   P2P_CHECK(f != WireFormat::Mxfp6, "host_verify_wire_reduced_packed: mxfp6 images are summed to bf16 only (no requantised output yet)");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "host_verify_wire_reduced_packed: 1..8 operand seeds");
@@ -268,7 +279,7 @@ VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const 
     for (uint32_t i = 0; i < 16; ++i) {
       uint32_t w[kMaxWireReduceSrcs];
       for (int j = 0; j < nseeds; ++j) w[j] = x[j][2 * i] | static_cast<uint32_t>(x[j][2 * i + 1]) << 16;
-      sum[i] = wire_reduce_word(w, sb, nseeds, f);
+      sum[i] = wire_reduce_word(w, sb, nseeds, f, own_bf16);
       amax = std::max(amax, wire_word_amax(sum[i]));
     }
     const uint32_t out_sb = wire_scale_byte(amax, f);
@@ -420,17 +431,18 @@ class HostTransport final : public Transport {
 
   // ---- sum of wire images: each image into scratch, then the CPU sum ----
   bool supports_reduce_wire() const override { return true; }
+  void fill_wire_operand(void* p, size_t payload_bytes, uint64_t seed) override { host_fill_wire_operand(p, payload_bytes, seed); }
   VerifyResult verify_reduced_unpacked(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                       WireFormat fmt) override {
-    return host_verify_wire_reduced(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt);
+                                       WireFormat fmt, bool own_bf16) override {
+    return host_verify_wire_reduced(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, own_bf16);
   }
   void reduce_unpacked_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers, size_t,
-                            WireFormat fmt) override {
+                            WireFormat fmt, bool own_bf16) override {
     P2P_CHECK(in_group_ && !wire_reduce_.dst, "host transport: one reduce_unpacked_from per group, inside the group");
     P2P_CHECK(peers.size() < static_cast<size_t>(kMaxWireReduceSrcs),
               "host transport: a sum of wire images has at most 8 operands (the own one and 7 incoming)");
     const size_t image = wire_bytes(payload_bytes, fmt);
-    wire_reduce_ = {dst, payload_bytes, local_image, fmt, peers.size()};
+    wire_reduce_ = {dst, payload_bytes, local_image, fmt, peers.size(), false, own_bf16};
     if (scratch_.size() < image * peers.size()) scratch_.resize(image * peers.size());
     for (size_t i = 0; i < peers.size(); ++i) {
       P2P_CHECK(peers[i] >= 0 && peers[i] < n_, "bad peer");
@@ -439,12 +451,12 @@ class HostTransport final : public Transport {
   }
   // --reduce-out wire: the same receives, the sum packed again in group_end().
   VerifyResult verify_reduced_packed(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                     WireFormat fmt) override {
-    return host_verify_wire_reduced_packed(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt);
+                                     WireFormat fmt, bool own_bf16) override {
+    return host_verify_wire_reduced_packed(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, own_bf16);
   }
   void reduce_packed_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
-                          size_t src_offset, WireFormat fmt) override {
-    reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt);
+                          size_t src_offset, WireFormat fmt, bool own_bf16) override {
+    reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt, own_bf16);
     wire_reduce_.packed = true;
   }
 
@@ -487,7 +499,7 @@ class HostTransport final : public Transport {
       std::vector<const void*> images{wire_reduce_.local_image};
       for (size_t i = 0; i < wire_reduce_.npeers; ++i) images.push_back(scratch_.data() + i * image);
       (wire_reduce_.packed ? host_wire_reduce_packed : host_wire_reduce)(wire_reduce_.dst, images.data(), static_cast<int>(images.size()),
-                                                                         wire_reduce_.bytes, wire_reduce_.fmt);
+                                                                         wire_reduce_.bytes, wire_reduce_.fmt, wire_reduce_.own_bf16);
     }
     wire_reduce_ = {};
     // Injected skip fault: the images were read off the wire and are dropped.
@@ -519,6 +531,7 @@ class HostTransport final : public Transport {
     WireFormat fmt = WireFormat::Off;
     size_t npeers = 0;
     bool packed = false;  // reduce_packed_from: dst receives the sum's wire image
+    bool own_bf16 = false;  // local_image is the own shard in bf16
   };
   struct PendingUnpack {
     void* dst;

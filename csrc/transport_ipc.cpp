@@ -319,7 +319,7 @@ class IpcTransport final : public GpuTransport {
   // one launch per group (kernels.hpp launch_wire_reduce).
   bool supports_reduce_wire() const override { return engine_ == "kernel"; }
   void reduce_unpacked_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
-                            size_t src_offset, WireFormat fmt) override {
+                            size_t src_offset, WireFormat fmt, bool own_bf16) override {
     P2P_CHECK(supports_reduce_wire(), "ipc transport: --reduce-wire needs --ipc-engine kernel");
     P2P_CHECK(in_group_ && !wire_reduce_.dst, "ipc transport: one reduce_unpacked_from per group, inside the group");
     P2P_CHECK(peers.size() < static_cast<size_t>(kMaxWireReduceSrcs),
@@ -334,6 +334,7 @@ class IpcTransport final : public GpuTransport {
     wire_reduce_ = {};
     wire_reduce_.dst = dst;
     wire_reduce_.payload_bytes = payload_bytes;
+    wire_reduce_.own_bf16 = own_bf16;  // local_image: the own shard in bf16, local memory
     wire_reduce_.src[wire_reduce_.nsrc++] = local_image;
     for (int peer : peers) {
       P2P_CHECK(peer >= 0 && peer < n_, "bad peer");
@@ -346,8 +347,8 @@ class IpcTransport final : public GpuTransport {
   // --reduce-out wire: the same op, launched as the wire-reduce-pack kernel
   // (kernels.hpp launch_wire_reduce_packed): dst receives the sum's image.
   void reduce_packed_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
-                          size_t src_offset, WireFormat fmt) override {
-    reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt);
+                          size_t src_offset, WireFormat fmt, bool own_bf16) override {
+    reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt, own_bf16);
     wire_reduce_packed_ = true;
   }
 

@@ -136,6 +136,45 @@ __device__ __forceinline__ void store_block(const u32x4 (&v)[4], char* pd, uint3
   }
 }
 
+// store_block's mirror, the load of a lane's own 64 B of bf16 (the sum's own
+// shard, wire_reduce_op.hpp own_bf16): block wave_block + lane of a tile of nb
+// blocks whose payload begins at ps, local memory.  Split in two so that the
+// global loads can be issued with the tile's other loads and the LDS exchange
+// waits for them alone.  SPLIT: the wave reads its 4 KiB as four fully
+// coalesced 16 B loads (load_block: instruction i covers bytes 1024 i ..
+// 1024 i + 1023 of the wave's payload, lane l the chunk l % 4 of row
+// 16 i + l / 4), writes them into its slot under the store path's swizzle and
+// reads its own row back as four ds_read_b128 (load_block_rows), conflict-free
+// both ways for the reason given above.  The slot is the one store_block uses
+// later in the tile; the fences here and there order the two uses for the
+// compiler.  Contiguous: four 16 B loads straight from the lane's block, a
+// 64 B lane stride.  A chunk past the tile's end is read from the tile's first
+// 16 B instead (every tile has a block): its lane stores nothing.
+template <bool SPLIT>
+__device__ __forceinline__ void load_block(u32x4 (&g)[4], const char* ps, uint32_t nb, uint32_t wave_block, uint32_t lane) {
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) {
+    const uint32_t off = SPLIT ? kWireBlockBytes * wave_block + 1024u * i + 16u * lane
+                               : kWireBlockBytes * (wave_block + lane) + 16u * i;
+    g[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ps + (off / kWireBlockBytes < nb ? off : 0u)));
+  }
+}
+template <bool SPLIT>
+__device__ __forceinline__ void load_block_rows(u32x4 (&g)[4], uint32_t lane, char* slot) {
+  if constexpr (SPLIT) {
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+      const uint32_t row = 16u * i + (lane >> 2), chunk = lane & 3u;
+      *reinterpret_cast<u32x4*>(slot + 64u * row + 16u * (chunk ^ ((row >> 2) & 3u))) = g[i];
+    }
+    wave_lds_fence();
+    const uint32_t wsw = (lane >> 2) & 3u;
+#pragma unroll
+    for (uint32_t c = 0; c < 4; ++c) g[c] = *reinterpret_cast<const u32x4*>(slot + 64u * lane + 16u * (c ^ wsw));
+    wave_lds_fence();  // the store stage's writes stay behind these reads
+  }
+}
+
 }  // namespace wire6
 }  // namespace dev
 }  // namespace p2p

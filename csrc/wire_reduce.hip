@@ -31,6 +31,14 @@
 //   * mxfp6 widens a whole block per lane and instruction: wire_reduce6_kernel
 //     below, a lane per block and 32 accumulators, behind the same launcher;
 //     wire6_lane.hpp has its geometry and its two store paths.
+//   * A bf16 own shard (WireReduceOp::own_bf16, --reduce-own bf16): OWN is a
+//     template parameter beside K and the format, so the all-image kernels
+//     are what they were.  Source 0 is then payload bytes of bf16 in local
+//     memory: a lane loads the 16 elements it accumulates as two 16 B
+//     non-temporal loads ahead of the images' loads (split: 4 KiB apart, both
+//     coalesced, the mirror of the stores; contiguous: its 32 B) and widens
+//     them with shifts and masks into the accumulators.  mxfp6, a block per
+//     lane: wire6_lane.hpp load_block.
 //   * No packed f32 instructions in this object (Makefile): the add chains
 //     stay scalar f32 adds.
 #include <hip/hip_runtime.h>
@@ -41,6 +49,7 @@
 #include "hip_check.hpp"
 #include "kernels.hpp"
 #include "wire6_lane.hpp"
+#include "wire_own_lane.hpp"
 
 namespace p2p {
 namespace dev {
@@ -113,7 +122,12 @@ __device__ __forceinline__ void load_desc(__amdgpu_buffer_rsrc_t rs, int r0, int
   s1 = SPLIT ? __builtin_amdgcn_raw_buffer_load_b8(rs, q1, 0, AUX) : s0;
 }
 
-template <WireFormat F, int K, bool SPLIT>
+using wire_own::load_own;  // the own shard's load side: wire_own_lane.hpp
+using wire_own::widen_own;
+
+// OWN: source 0 is the receiver's own shard in bf16 (local memory), not an
+// image; it begins the chains as it is and sources 1..K-1 follow as before.
+template <WireFormat F, int K, bool SPLIT, bool OWN>
 __global__ __launch_bounds__(kBlock) void wire_reduce_kernel(const WireReduceArgs a) {
   constexpr uint32_t EB = wire_block_elem_bytes(F);
   constexpr uint32_t kFullTile = wire_tile_bytes(kWireTileBlocks, F);
@@ -134,13 +148,16 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_kernel(const WireReduceArg
     // conversion, and nothing else writes these registers in between (no
     // zero-fill of the lanes past the end): the wave waits once per tile.
     uint32_t w0[K][EW], w1[K][EW], s0[K], s1[K];
+    constexpr int K0 = OWN ? 1 : 0;  // the first source that is an image
+    u32x4 h0, h1;                    // OWN: the own shard's 16 elements, issued first
+    if constexpr (OWN) load_own(a.src[0] + t * kWireTilePayload, e0, e1, in0, in1, h0, h1);
     if ((a.coherent & ((1u << K) - 1u)) == 0) {
       // Every image is local: straight-line non-temporal loads; a lane past
       // the tile's end re-reads the tile's first unit and stores nothing.
       const uint32_t l0 = in0 ? c0 : 0, l1 = in1 ? c1 : 0;
       const uint32_t b0 = in0 ? e0 >> 5 : 0, b1 = in1 ? e1 >> 5 : 0;
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
+      for (int k = K0; k < K; ++k) {
         const char* ws = a.src[k] + t * kFullTile;
         if constexpr (!SPLIT && FP8) {
           const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ws + l0));
@@ -168,7 +185,7 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_kernel(const WireReduceArg
       const int r0 = static_cast<int>(in0 ? c0 : ebytes + nb), r1 = static_cast<int>(in1 ? c1 : ebytes + nb);
       const int q0 = static_cast<int>(ebytes + (e0 >> 5)), q1 = static_cast<int>(ebytes + (e1 >> 5));
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
+      for (int k = K0; k < K; ++k) {
         auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.src[k] + t * kFullTile), 0,
                                                     static_cast<int>(ebytes + nb), kRsrcFlags);
         if ((a.coherent >> k) & 1u)
@@ -179,8 +196,13 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_kernel(const WireReduceArg
     }
     // 16 accumulators: operand 0 begins the chains, the others add in order.
     float acc0[8], acc1[8];
-    widen8<F>(w0[0], scale_operand(s0[0]), acc0);
-    widen8<F>(w1[0], scale_operand(s1[0]), acc1);
+    if constexpr (OWN) {
+      widen_own(h0, acc0);
+      widen_own(h1, acc1);
+    } else {
+      widen8<F>(w0[0], scale_operand(s0[0]), acc0);
+      widen8<F>(w1[0], scale_operand(s1[0]), acc1);
+    }
 #pragma unroll
     for (int k = 1; k < K; ++k) {
       float x0[8], x1[8];
@@ -207,8 +229,20 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_kernel(const WireReduceArg
 // operand's 32 codes at once, 32 plain v_add_f32 per further operand in
 // operand order, 16 v_cvt_pk_bf16_f32.  Registers at K = 8: 48 of codes, 8
 // scale bytes, 32 accumulators and 32 of the operand being widened.
-template <int K, bool SPLIT>
-__global__ __launch_bounds__(wire6::kLanes) void wire_reduce6_kernel(const WireReduceArgs a) {
+// OWN: source 0 is the own shard in bf16, the lane's block 64 B of it.  Its
+// four 16 B loads are issued first (load_block: coalesced over the wave under
+// SPLIT), then the K - 1 images' loads; the wave then waits for the own data
+// alone, turns it into rows through its LDS slot (load_block_rows: the slot
+// the store stage uses at the end of the tile) and widens it with shifts and
+// masks into the 32 accumulators while the images are still in flight.
+// Registers: left to itself the K = 8 split OWN instantiation takes 130 VGPRs,
+// two above the 128 that still fit 4 waves per SIMD (the all-image one takes
+// 127).  OWN therefore asks for those 4 waves, and the compiler schedules it
+// into 128 without a spill (docs/DESIGN.md); the all-image instantiations keep
+// the default bound (at least one wave) and their code.
+template <int K, bool SPLIT, bool OWN>
+__global__ __launch_bounds__(wire6::kLanes) __attribute__((amdgpu_waves_per_eu(OWN ? 4 : 1))) void wire_reduce6_kernel(
+    const WireReduceArgs a) {
   using wire6::kF, wire6::kEB, wire6::kFullTile, wire6::kLanes, wire6::kTilesPerGroup, wire6::kSlotBytes, wire6::kTileLanes;
   using wire6::u32x6, wire6::f32x32, wire6::load_codes, wire6::store_block;
   __shared__ __attribute__((aligned(16))) char slots[SPLIT ? (kLanes / 64) * kSlotBytes : 16];
@@ -225,11 +259,14 @@ __global__ __launch_bounds__(wire6::kLanes) void wire_reduce6_kernel(const WireR
     const bool in = blk < nb;
     u32x6 codes[K];
     uint32_t sb[K];
+    constexpr int K0 = OWN ? 1 : 0;  // the first source that is an image
+    u32x4 own[4];
+    if constexpr (OWN) wire6::load_block<SPLIT>(own, a.src[0] + t * kWireTilePayload, nb, wave_block, lane);
     if ((a.coherent & ((1u << K) - 1u)) == 0) {
       // Every image is local: a lane past the tile's end re-reads its first block.
       const uint32_t at = in ? kEB * blk : 0, sat = soff + (in ? blk : 0);
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
+      for (int k = K0; k < K; ++k) {
         const char* ws = a.src[k] + t * kFullTile;
         codes[k] = load_codes(ws + at);
         sb[k] = reinterpret_cast<const uint8_t*>(ws)[sat];
@@ -239,7 +276,7 @@ __global__ __launch_bounds__(wire6::kLanes) void wire_reduce6_kernel(const WireR
       // aims at its end and loads 0.  The uniform branch picks the cache policy.
       const int at = static_cast<int>(in ? kEB * blk : soff + nb), sat = static_cast<int>(soff + blk);
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
+      for (int k = K0; k < K; ++k) {
         auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.src[k] + t * kFullTile), 0,
                                                     static_cast<int>(soff + nb), kRsrcFlags);
         if ((a.coherent >> k) & 1u) {
@@ -251,7 +288,17 @@ __global__ __launch_bounds__(wire6::kLanes) void wire_reduce6_kernel(const WireR
         }
       }
     }
-    f32x32 acc = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(codes[0], scale_operand(sb[0]));
+    f32x32 acc;
+    if constexpr (OWN) {
+      wire6::load_block_rows<SPLIT>(own, lane, slot);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        acc[2 * j] = __builtin_bit_cast(float, own[j / 4][j % 4] << 16);
+        acc[2 * j + 1] = __builtin_bit_cast(float, own[j / 4][j % 4] & 0xFFFF0000u);
+      }
+    } else {
+      acc = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(codes[0], scale_operand(sb[0]));
+    }
 #pragma unroll
     for (int k = 1; k < K; ++k) {
       const f32x32 x = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(codes[k], scale_operand(sb[k]));
@@ -270,6 +317,7 @@ __global__ __launch_bounds__(wire6::kLanes) void wire_reduce6_kernel(const WireR
 struct SeedArgs {
   uint64_t seed[kMaxWireReduceSrcs];
   int n;
+  bool own_bf16;  // operand 0 is the raw stream, not its image
 };
 
 struct Partial {
@@ -299,7 +347,7 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_kernel(const uint4
       const uint32_t sb = wire_scale_byte(amax, F);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const uint32_t x = wire_roundtrip_word(w[c], sb, F);
+        const uint32_t x = k == 0 && s.own_bf16 ? w[c] : wire_roundtrip_word(w[c], sb, F);
         if (k == 0) sum[c] = reduce_begin(x, ReduceType::Bf16);
         else reduce_add(sum[c], x, ReduceType::Bf16);
       }
@@ -343,6 +391,23 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_kernel(const uint4
   }
 }
 
+// ------------------------------------------------------------ own-shard fill ----
+
+// bf16 of operand stream `seed` (wire_operand_word), what fill_packed_kernel
+// quantises: a 16 B vector per lane, the fill kernels' grid-stride geometry.
+__global__ __launch_bounds__(kBlock) void fill_wire_operand_kernel(uint4* __restrict__ p, uint64_t nvec, uint64_t seed) {
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kBlock; base < nvec; base += static_cast<uint64_t>(gridDim.x) * kBlock) {
+    const uint32_t key = prng_key(seed, base * 4);  // block-uniform: scalar ALU
+    const uint64_t i = base + threadIdx.x;
+    if (i < nvec) {
+      uint32_t w[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) w[c] = wire_operand_word(prng_word_k(key, static_cast<uint32_t>(i * 4 + c)), i * 4 + c);
+      p[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ launch ----
 
 void check_format(WireFormat f, size_t n, const char* who) {
@@ -350,17 +415,27 @@ void check_format(WireFormat f, size_t n, const char* who) {
   P2P_CHECK(n % kWireBlockBytes == 0, std::string(who) + ": the payload must be a multiple of 64 bytes (blocks of 32 bf16)");
 }
 
-template <WireFormat F, bool SPLIT, int K = kMaxWireReduceSrcs>
+template <WireFormat F, bool SPLIT, bool OWN, int K = kMaxWireReduceSrcs>
 void launch_wire_reduce_k(int nsrc, uint32_t grid, const WireReduceArgs& a, hipStream_t stream) {
   if constexpr (K < 1) {
     P2P_FATAL("wire_reduce: an op needs 1..8 sources");
   } else {
     if (nsrc != K)
-      launch_wire_reduce_k<F, SPLIT, K - 1>(nsrc, grid, a, stream);
+      launch_wire_reduce_k<F, SPLIT, OWN, K - 1>(nsrc, grid, a, stream);
     else if constexpr (F == WireFormat::Mxfp6)
-      wire_reduce6_kernel<K, SPLIT><<<(grid + wire6::kTilesPerGroup - 1) / wire6::kTilesPerGroup, wire6::kLanes, 0, stream>>>(a);
+      wire_reduce6_kernel<K, SPLIT, OWN><<<(grid + wire6::kTilesPerGroup - 1) / wire6::kTilesPerGroup, wire6::kLanes, 0, stream>>>(a);
     else
-      wire_reduce_kernel<F, K, SPLIT><<<grid, kBlock, 0, stream>>>(a);
+      wire_reduce_kernel<F, K, SPLIT, OWN><<<grid, kBlock, 0, stream>>>(a);
+  }
+}
+template <WireFormat F>
+void launch_wire_reduce_f(bool split, bool own, int nsrc, uint32_t grid, const WireReduceArgs& a, hipStream_t stream) {
+  if (own) {
+    if (split) launch_wire_reduce_k<F, true, true>(nsrc, grid, a, stream);
+    else launch_wire_reduce_k<F, false, true>(nsrc, grid, a, stream);
+  } else {
+    if (split) launch_wire_reduce_k<F, true, false>(nsrc, grid, a, stream);
+    else launch_wire_reduce_k<F, false, false>(nsrc, grid, a, stream);
   }
 }
 
@@ -369,6 +444,7 @@ void launch_wire_reduce_k(int nsrc, uint32_t grid, const WireReduceArgs& a, hipS
 void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks, WireLanes lanes) {
   check_format(fmt, op.payload_bytes, "wire_reduce");
   P2P_CHECK(op.nsrc >= 1 && op.nsrc <= kMaxWireReduceSrcs, "wire_reduce: an op needs 1..8 sources");
+  P2P_CHECK(!op.own_bf16 || !(op.coherent_mask & 1u), "wire_reduce: a bf16 own shard (source 0) is local memory, not a peer's buffer");
   if (!op.payload_bytes) return;
   P2P_CHECK(op.dst && reinterpret_cast<uintptr_t>(op.dst) % 16 == 0, "wire_reduce: 16-byte aligned buffers required");
   WireReduceArgs a{};
@@ -385,27 +461,31 @@ void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stre
   const uint32_t grid = static_cast<uint32_t>(std::min(a.ntiles, cap));
   // Auto: split was measured faster, or level, for every format at every fan-in (docs/DESIGN.md).
   const bool split = lanes == WireLanes::Auto ? true : lanes == WireLanes::Split;
-  if (fmt == WireFormat::Mxfp6) {
-    if (split) launch_wire_reduce_k<WireFormat::Mxfp6, true>(op.nsrc, grid, a, stream);
-    else launch_wire_reduce_k<WireFormat::Mxfp6, false>(op.nsrc, grid, a, stream);
-  } else if (fmt == WireFormat::Mxfp8) {
-    if (split) launch_wire_reduce_k<WireFormat::Mxfp8, true>(op.nsrc, grid, a, stream);
-    else launch_wire_reduce_k<WireFormat::Mxfp8, false>(op.nsrc, grid, a, stream);
-  } else {
-    if (split) launch_wire_reduce_k<WireFormat::Mxfp4, true>(op.nsrc, grid, a, stream);
-    else launch_wire_reduce_k<WireFormat::Mxfp4, false>(op.nsrc, grid, a, stream);
-  }
+  if (fmt == WireFormat::Mxfp6) launch_wire_reduce_f<WireFormat::Mxfp6>(split, op.own_bf16, op.nsrc, grid, a, stream);
+  else if (fmt == WireFormat::Mxfp8) launch_wire_reduce_f<WireFormat::Mxfp8>(split, op.own_bf16, op.nsrc, grid, a, stream);
+  else launch_wire_reduce_f<WireFormat::Mxfp4>(split, op.own_bf16, op.nsrc, grid, a, stream);
+  HIPCHECK(hipGetLastError());
+}
+
+void launch_fill_wire_operand(void* p, size_t payload_bytes, uint64_t seed, hipStream_t stream) {
+  P2P_CHECK(payload_bytes % kWireBlockBytes == 0, "fill_wire_operand: the payload must be a multiple of 64 bytes (blocks of 32 bf16)");
+  if (!payload_bytes) return;
+  P2P_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, "fill_wire_operand: buffer must be 16-byte aligned");
+  const uint64_t nvec = payload_bytes / 16;
+  const unsigned grid = static_cast<unsigned>(std::min((nvec + kBlock - 1) / kBlock, kMaxGrid));
+  fill_wire_operand_kernel<<<grid, kBlock, 0, stream>>>(static_cast<uint4*>(p), nvec, seed);
   HIPCHECK(hipGetLastError());
 }
 
 void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint64_t* seeds, int nseeds, WireFormat fmt,
-                                VerifyAccum* acc, hipStream_t stream) {
+                                VerifyAccum* acc, hipStream_t stream, bool own_bf16) {
   check_format(fmt, payload_bytes, "verify_wire_reduced");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "verify_wire_reduced: 1..8 operand seeds");
   if (payload_bytes) {
     P2P_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, "verify_wire_reduced: buffer must be 16-byte aligned");
     SeedArgs s{};
     s.n = nseeds;
+    s.own_bf16 = own_bf16;
     for (int k = 0; k < nseeds; ++k) s.seed[k] = seeds[k];
     const uint64_t nvec = payload_bytes / 16;
     const uint64_t cap = static_cast<uint64_t>(cu_count()) * kVerifyPerCu;

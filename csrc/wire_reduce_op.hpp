@@ -28,6 +28,21 @@
 // it, and its largest operand 7.5 x 2^(109 - 127) < 2^-15, so eight of them
 // stay below 2^-12: the same argument holds with room to spare.
 //
+// A bf16 own shard (own_bf16, --reduce-own bf16).  A real receiver holds its
+// local shard in bf16 and only what arrives is quantised: operand 0 is then the
+// raw word of the receiver's operand stream (wire_operand_word), operands
+// 1..K-1 stay round-tripped images.  Chain, order and the one rounding are the
+// same.  Range: the own operand's exponent field lies in [64, 110], so its
+// magnitude is at least 2^(64 - 127) = 2^-63 with a 7-bit significand, a
+// multiple of 2^-70 and therefore of every granule above (2^-80, 2^-68,
+// 2^-66): partial sums stay multiples of the old granule and a non-zero one is
+// still at least 2^-80.  It is below 2^(111 - 127) = 2^-16, so own + 7 incoming
+// is below 2^-16 + 7 x 2^-9 < 2^-6, the bound that held for eight images.  No
+// subnormal, no overflow, and the sum's range [2^-80, 2^-6) is the one the
+// requantised output's argument below starts from: its scale-byte clamp still
+// never acts.  K = 1 is a copy of the own shard (widening a normal bf16 to f32
+// and rounding it back is exact, zeros keep their sign), or its pack.
+//
 // Zeros are real operands here, unlike in reduce_op.hpp: the codes 0x00 / 0x80
 // (mxfp8), 0x00 / 0x20 (mxfp6) and 0x0 / 0x8 (mxfp4) occur, and the sign of a zero is kept by the
 // dequantisation.  Signed zeros follow IEEE addition in round-to-nearest:
@@ -69,20 +84,26 @@ constexpr int kMaxWireReduceSrcs = 8;  // operands of one sum: the own image and
 
 // One 32-bit word (two elements) of the sum.  w[k] is operand k's word of its
 // operand stream (wire_operand_word), sb[k] the scale byte of the block that
-// word lies in; k in 1..kMaxWireReduceSrcs.
-P2P_HD uint32_t wire_reduce_word(const uint32_t* w, const uint32_t* sb, int k, WireFormat f) {
-  ReduceAcc a = reduce_begin(wire_roundtrip_word(w[0], sb[0], f), ReduceType::Bf16);
+// word lies in; k in 1..kMaxWireReduceSrcs.  own_bf16: operand 0 enters as it
+// is, not as its image (sb[0] is not read).
+P2P_HD uint32_t wire_reduce_word(const uint32_t* w, const uint32_t* sb, int k, WireFormat f, bool own_bf16 = false) {
+  ReduceAcc a = reduce_begin(own_bf16 ? w[0] : wire_roundtrip_word(w[0], sb[0], f), ReduceType::Bf16);
   for (int i = 1; i < k; ++i) reduce_add(a, wire_roundtrip_word(w[i], sb[i], f), ReduceType::Bf16);
   return reduce_finish(a, ReduceType::Bf16);
 }
 
 // Host side (transport_host.cpp).  n is the payload size, a multiple of 64.
 // out: n bytes of bf16 = the sum of the k wire images (wire_bytes(n, f) each)
-// in order.  Any alignment.
-void host_wire_reduce(void* out, const void* const* images, int k, size_t n, WireFormat f);
+// in order.  Any alignment.  own_bf16: images[0] is n bytes of bf16, the
+// receiver's own shard, not an image.
+void host_wire_reduce(void* out, const void* const* images, int k, size_t n, WireFormat f, bool own_bf16 = false);
 // Compares p with the sum of the operand streams `seeds` (operand order), each
-// packed and unpacked by the shared functions; a wrong 32-bit word counts once.
-VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f);
+// packed and unpacked by the shared functions (own_bf16: all but the first); a
+// wrong 32-bit word counts once.
+VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f,
+                                      bool own_bf16 = false);
+// n bytes of bf16: operand stream `seed` as a receiver holds its own shard.
+void host_fill_wire_operand(void* p, size_t n, uint64_t seed);
 
 // ---- requantised output (--reduce-out wire) ----
 // The largest magnitude (bits & 0x7FFF) of the two bf16 halves of a sum word.
@@ -101,11 +122,12 @@ P2P_HD uint32_t wire_code_word(const uint32_t* w, uint32_t sb, WireFormat f) {
 }
 // out_image: wire_bytes(n, f) bytes = the wire image (padding zeroed) of the
 // sum host_wire_reduce gives for the k images.  Any alignment.
-void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f);
+void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f, bool own_bf16 = false);
 // Compares `image` with the packed sum of the operand streams `seeds`: a wrong
 // 32-bit word of element codes counts once, a wrong scale byte once, first_bad
 // is the lowest byte offset in the image of either, the checksum is the sum
 // of the code words and the scale bytes.  The padding is not read.
-VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f);
+VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f,
+                                             bool own_bf16 = false);
 
 }  // namespace p2p

@@ -44,6 +44,7 @@
 #include "common.hpp"
 #include "hip_check.hpp"
 #include "kernels.hpp"
+#include "wire_own_lane.hpp"
 
 namespace p2p {
 namespace dev {
@@ -161,7 +162,11 @@ __device__ __forceinline__ void load_desc(__amdgpu_buffer_rsrc_t rs, int r0, int
   s1 = SPLIT ? __builtin_amdgcn_raw_buffer_load_b8(rs, q1, 0, AUX) : s0;
 }
 
-template <WireFormat F, int K, bool SPLIT>
+using wire_own::load_own;  // the own shard's load side: wire_own_lane.hpp
+using wire_own::widen_own;
+
+// OWN: source 0 is the receiver's own shard in bf16 (local memory), not an image.
+template <WireFormat F, int K, bool SPLIT, bool OWN>
 __global__ __launch_bounds__(kBlock) void wire_reduce_pack_kernel(const ReducePackArgs a) {
   constexpr uint32_t EB = wire_block_elem_bytes(F);
   constexpr uint32_t kFullTile = wire_tile_bytes(kWireTileBlocks, F);
@@ -184,13 +189,16 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_pack_kernel(const ReducePa
     const bool in0 = blk0 < nb, in1 = blk1 < nb;
     // All K element loads and all K scale loads before the first conversion.
     uint32_t w0[K][EW], w1[K][EW], s0[K], s1[K];
+    constexpr int K0 = OWN ? 1 : 0;  // the first source that is an image
+    u32x4 own0, own1;                // OWN: the own shard's 16 elements, issued first
+    if constexpr (OWN) load_own(a.src[0] + t * kWireTilePayload, e0, e1, in0, in1, own0, own1);
     if ((a.coherent & ((1u << K) - 1u)) == 0) {
       // Every image is local: straight-line non-temporal loads; a lane past
       // the tile's end re-reads the tile's first unit and stores nothing.
       const uint32_t l0 = in0 ? c0 : 0, l1 = in1 ? c1 : 0;
       const uint32_t b0 = in0 ? blk0 : 0, b1 = in1 ? blk1 : 0;
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
+      for (int k = K0; k < K; ++k) {
         const char* ws = a.src[k] + t * kFullTile;
         if constexpr (!SPLIT && FP8) {
           const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ws + l0));
@@ -217,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_pack_kernel(const ReducePa
       const int r0 = static_cast<int>(in0 ? c0 : ebytes + nb), r1 = static_cast<int>(in1 ? c1 : ebytes + nb);
       const int q0 = static_cast<int>(ebytes + blk0), q1 = static_cast<int>(ebytes + blk1);
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
+      for (int k = K0; k < K; ++k) {
         auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.src[k] + t * kFullTile), 0,
                                                     static_cast<int>(ebytes + nb), kRsrcFlags);
         if ((a.coherent >> k) & 1u)
@@ -228,8 +236,13 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_pack_kernel(const ReducePa
     }
     // 16 accumulators: operand 0 begins the chains, the others add in order.
     float acc0[8], acc1[8];
-    widen8<F>(w0[0], scale_operand(s0[0]), acc0);
-    widen8<F>(w1[0], scale_operand(s1[0]), acc1);
+    if constexpr (OWN) {
+      widen_own(own0, acc0);
+      widen_own(own1, acc1);
+    } else {
+      widen8<F>(w0[0], scale_operand(s0[0]), acc0);
+      widen8<F>(w1[0], scale_operand(s1[0]), acc1);
+    }
 #pragma unroll
     for (int k = 1; k < K; ++k) {
       float x0[8], x1[8];
@@ -280,6 +293,7 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_pack_kernel(const ReducePa
 struct SeedArgs {
   uint64_t seed[kMaxWireReduceSrcs];
   int n;
+  bool own_bf16;  // operand 0 is the raw stream, not its image
 };
 
 struct Partial {
@@ -314,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_packed_kernel(cons
       const uint32_t sb = wire_scale_byte(amax, F);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const uint32_t x = wire_roundtrip_word(w[c], sb, F);
+        const uint32_t x = k == 0 && s.own_bf16 ? w[c] : wire_roundtrip_word(w[c], sb, F);
         if (k == 0) sum[c] = reduce_begin(x, ReduceType::Bf16);
         else reduce_add(sum[c], x, ReduceType::Bf16);
       }
@@ -393,15 +407,25 @@ uint32_t last_blocks_of(size_t n) {
   return static_cast<uint32_t>(rest ? rest / kWireBlockBytes : kWireTileBlocks);
 }
 
-template <WireFormat F, bool SPLIT, int K = kMaxWireReduceSrcs>
+template <WireFormat F, bool SPLIT, bool OWN, int K = kMaxWireReduceSrcs>
 void launch_k(int nsrc, uint32_t grid, const ReducePackArgs& a, hipStream_t stream) {
   if constexpr (K < 1) {
     P2P_FATAL("wire_reduce_packed: an op needs 1..8 sources");
   } else {
     if (nsrc == K)
-      wire_reduce_pack_kernel<F, K, SPLIT><<<grid, kBlock, 0, stream>>>(a);
+      wire_reduce_pack_kernel<F, K, SPLIT, OWN><<<grid, kBlock, 0, stream>>>(a);
     else
-      launch_k<F, SPLIT, K - 1>(nsrc, grid, a, stream);
+      launch_k<F, SPLIT, OWN, K - 1>(nsrc, grid, a, stream);
+  }
+}
+template <WireFormat F>
+void launch_f(bool split, bool own, int nsrc, uint32_t grid, const ReducePackArgs& a, hipStream_t stream) {
+  if (own) {
+    if (split) launch_k<F, true, true>(nsrc, grid, a, stream);
+    else launch_k<F, false, true>(nsrc, grid, a, stream);
+  } else {
+    if (split) launch_k<F, true, false>(nsrc, grid, a, stream);
+    else launch_k<F, false, false>(nsrc, grid, a, stream);
   }
 }
 
@@ -410,6 +434,7 @@ void launch_k(int nsrc, uint32_t grid, const ReducePackArgs& a, hipStream_t stre
 void launch_wire_reduce_packed(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks, WireLanes lanes) {
   check_format(fmt, op.payload_bytes, "wire_reduce_packed");
   P2P_CHECK(op.nsrc >= 1 && op.nsrc <= kMaxWireReduceSrcs, "wire_reduce_packed: an op needs 1..8 sources");
+  P2P_CHECK(!op.own_bf16 || !(op.coherent_mask & 1u), "wire_reduce_packed: a bf16 own shard (source 0) is local memory, not a peer's buffer");
   if (!op.payload_bytes) return;
   P2P_CHECK(op.dst && reinterpret_cast<uintptr_t>(op.dst) % 16 == 0, "wire_reduce_packed: 16-byte aligned buffers required");
   ReducePackArgs a{};
@@ -426,24 +451,20 @@ void launch_wire_reduce_packed(const WireReduceOp& op, WireFormat fmt, hipStream
   // Auto: contiguous was measured faster in every cell, by 1-8% against a spread under 1% (docs/DESIGN.md): unlike
   // wire_reduce.hip, where split's two coalesced 16 B stores win.
   const bool split = lanes == WireLanes::Auto ? false : lanes == WireLanes::Split;
-  if (fmt == WireFormat::Mxfp8) {
-    if (split) launch_k<WireFormat::Mxfp8, true>(op.nsrc, grid, a, stream);
-    else launch_k<WireFormat::Mxfp8, false>(op.nsrc, grid, a, stream);
-  } else {
-    if (split) launch_k<WireFormat::Mxfp4, true>(op.nsrc, grid, a, stream);
-    else launch_k<WireFormat::Mxfp4, false>(op.nsrc, grid, a, stream);
-  }
+  if (fmt == WireFormat::Mxfp8) launch_f<WireFormat::Mxfp8>(split, op.own_bf16, op.nsrc, grid, a, stream);
+  else launch_f<WireFormat::Mxfp4>(split, op.own_bf16, op.nsrc, grid, a, stream);
   HIPCHECK(hipGetLastError());
 }
 
 void launch_verify_wire_reduced_packed(const void* image, size_t payload_bytes, const uint64_t* seeds, int nseeds,
-                                       WireFormat fmt, VerifyAccum* acc, hipStream_t stream) {
+                                       WireFormat fmt, VerifyAccum* acc, hipStream_t stream, bool own_bf16) {
   check_format(fmt, payload_bytes, "verify_wire_reduced_packed");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "verify_wire_reduced_packed: 1..8 operand seeds");
   if (payload_bytes) {
     P2P_CHECK(reinterpret_cast<uintptr_t>(image) % 16 == 0, "verify_wire_reduced_packed: buffer must be 16-byte aligned");
     SeedArgs s{};
     s.n = nseeds;
+    s.own_bf16 = own_bf16;
     for (int k = 0; k < nseeds; ++k) s.seed[k] = seeds[k];
     const uint64_t nvec = payload_bytes / 16;
     const uint64_t cap = static_cast<uint64_t>(cu_count()) * kVerifyPerCu;

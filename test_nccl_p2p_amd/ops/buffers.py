@@ -368,51 +368,61 @@ def reference_wire_roundtrip(words: torch.Tensor, fmt: str) -> torch.Tensor:
 
 
 def wire_reduce_(dst: torch.Tensor, srcs, fmt: str, *, coherent=False, max_blocks: int = 0,
-                 lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+                 lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None, own_bf16: bool = False) -> torch.Tensor:
     """The bytes of ``dst`` as bf16 = the sum of the 1..8 'mxfp8' / 'mxfp6' /
     'mxfp4' wire images ``srcs`` in that order, dequantised and added in float32
     and rounded once, with the gfx950 wire-reduce kernel (the IPC pull engine's
     receive under ``--reduce-wire``; stream-ordered).  ``coherent``: True reads
-    every image in the cross-GPU form, an int is a mask, bit k for source k."""
+    every image in the cross-GPU form, an int is a mask, bit k for source k.
+    ``own_bf16``: ``srcs[0]`` is the receiver's own shard, the payload's bytes
+    of bf16 in local memory, and enters the sum unquantised (``--reduce-own
+    bf16``); bit 0 of the mask must be clear."""
     nbytes = _check_tensor(dst)
     nat = require_native()
-    if any(_check_tensor(s) < nat.wire_bytes(nbytes, fmt) for s in srcs):
-        raise ValueError("wire_reduce_: a source holds less than wire_bytes() of dst")
-    nat.wire_reduce(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, fmt, _stream(stream), coherent, max_blocks, lanes)
+    if any(_check_tensor(s) < (nbytes if own_bf16 and k == 0 else nat.wire_bytes(nbytes, fmt)) for k, s in enumerate(srcs)):
+        raise ValueError("wire_reduce_: a source holds less than wire_bytes() of dst (own_bf16: the first less than dst)")
+    nat.wire_reduce(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, fmt, _stream(stream), coherent, max_blocks, lanes,
+                    own_bf16)
     return dst
 
 
-def reference_wire_reduce(operands, fmt: str) -> torch.Tensor:
+def reference_wire_reduce(operands, fmt: str, own_bf16: bool = False) -> torch.Tensor:
     """What :func:`wire_reduce_` leaves (uint8, bf16 payload bytes) for the
     images of ``operands`` (int64 bf16 word tensors, in order):
     :func:`reference_wire_roundtrip` of each (float64 quantisation) fed to
     :func:`reference_reduce` as bf16 (a ``torch.float32`` add chain on the CPU
-    and one ``.to(torch.bfloat16)``)."""
+    and one ``.to(torch.bfloat16)``).  ``own_bf16``: ``operands[0]`` is the
+    own shard and enters unquantised."""
     widened = []
-    for w in operands:
+    for k, w in enumerate(operands):
+        if own_bf16 and k == 0:
+            widened.append(w.cpu())
+            continue
         b = reference_wire_roundtrip(w, fmt).to(torch.int64).reshape(-1, 4)
         widened.append(b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16) | (b[:, 3] << 24))
     return words_to_bytes(reference_reduce(widened, "bf16"))
 
 
-def wire_reduce_packed_(dst: torch.Tensor, srcs, nbytes: int, fmt: str, *, coherent: bool = False, max_blocks: int = 0,
-                        lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+def wire_reduce_packed_(dst: torch.Tensor, srcs, nbytes: int, fmt: str, *, coherent=False, max_blocks: int = 0,
+                        lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None, own_bf16: bool = False) -> torch.Tensor:
     """``dst`` = the wire image (``wire_bytes(nbytes, fmt)`` bytes) of the bf16
     sum :func:`wire_reduce_` gives for the 1..8 wire images ``srcs`` of
     ``nbytes`` of payload each, with the gfx950 wire-reduce-pack kernel in one
-    launch (the IPC pull engine's receive under ``--reduce-out wire``)."""
+    launch (the IPC pull engine's receive under ``--reduce-out wire``).
+    ``coherent`` and ``own_bf16`` as in :func:`wire_reduce_`."""
     nat = require_native()
     image = nat.wire_bytes(nbytes, fmt)
-    if _check_tensor(dst) < image or any(_check_tensor(s) < image for s in srcs):
+    if _check_tensor(dst) < image or any(_check_tensor(s) < (nbytes if own_bf16 and k == 0 else image) for k, s in enumerate(srcs)):
         raise ValueError("wire_reduce_packed_: dst or a source holds less than wire_bytes() of the payload")
-    nat.wire_reduce_packed(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, fmt, _stream(stream), coherent, max_blocks, lanes)
+    nat.wire_reduce_packed(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, fmt, _stream(stream), coherent, max_blocks, lanes,
+                           own_bf16)
     return dst
 
 
-def reference_wire_reduce_packed(operands, fmt: str) -> torch.Tensor:
+def reference_wire_reduce_packed(operands, fmt: str, own_bf16: bool = False) -> torch.Tensor:
     """What :func:`wire_reduce_packed_` leaves (uint8, the whole image):
     :func:`reference_wire_pack` of the :func:`reference_wire_reduce` result."""
-    b = reference_wire_reduce(operands, fmt).to(torch.int64).reshape(-1, 4)
+    b = reference_wire_reduce(operands, fmt, own_bf16).to(torch.int64).reshape(-1, 4)
     return reference_wire_pack(b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16) | (b[:, 3] << 24), fmt)
 
 
