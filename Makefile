@@ -26,7 +26,7 @@ HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
 CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o reduce.o wire.o wire_reduce.o wire_reduce_pack.o diagnose_hip.o pingpong.o stream.o load_hip.o)
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o reduce.o wire.o wire_reduce.o wire_reduce_pack.o wire_reduce_pack6.o diagnose_hip.o pingpong.o stream.o load_hip.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in
@@ -115,6 +115,10 @@ $(BUILD)/gpu/wire_reduce.o: csrc/wire_reduce.hip $(HEADERS) | $(BUILD)/gpu
 
 # The same sum with a requantised output: the same flags, the same scalar adds.
 $(BUILD)/gpu/wire_reduce_pack.o: csrc/wire_reduce_pack.hip $(HEADERS) | $(BUILD)/gpu
+	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
+# Its mxfp6 form, a kernel of its own in an object of its own (the two compile side by side).
+$(BUILD)/gpu/wire_reduce_pack6.o: csrc/wire_reduce_pack6.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
 # csrc/diagnose.cpp (host side, in CORE) owns diagnose.o.

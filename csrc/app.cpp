@@ -150,7 +150,7 @@ data
                          timed and reported in payload bytes, the sum is checked bit for bit.
                          --transport ipc --ipc-engine kernel, or host; sizes multiples of 64;
                          not with --wire, --verify-inline, --diagnose, --reference or --resume
-      --reduce-out FORMAT  bf16 (default) | wire, with --reduce bf16 --reduce-wire F: what the sum
+      --reduce-out FORMAT  bf16 (default) | wire | both, with --reduce bf16 --reduce-wire F: what the sum
                          leaves.  wire: the middle hop of a quantised ring or combine.  One
                          launch of the gfx950 wire-reduce-pack kernel sums the images, rounds
                          the sum once to bf16, requantises it under each block's no-clip scale
@@ -158,14 +158,19 @@ data
                          --reduce-out bf16 followed by a pack would give, without the bf16
                          round trip through memory.  Flows stay in payload bytes; the image is
                          checked bit for bit.  Same transports and exclusions as --reduce-wire;
-                         F is mxfp8 or mxfp4 (mxfp6 sums to bf16 only)
+                         F is mxfp8 or mxfp4.  both: the turn-around hop of a two-shot
+                         quantised all-reduce: the same launch stores that image (for the
+                         peers to pull) and, in the receive slot, the bf16 it widens to, so
+                         the owner keeps exactly what its peers reconstruct; both outputs are
+                         checked bit for bit.  F is mxfp8, mxfp6 or mxfp4 (mxfp6: a kernel
+                         of its own, a lane per block)
       --reduce-own FORMAT  wire (default) | bf16, with --reduce bf16 --reduce-wire F: what operand 0
                          of a receiver's sum is.  bf16: the receiver's own shard as a real rank
                          holds it, bf16 that was never quantised (8 KiB per tile read, not the
                          image's 4.2 / 3.2 / 2.2 KiB); only what arrives is dequantised.  Still
                          one launch: the own shard begins the f32 chains, the incoming images
                          follow, one rounding.  Peers still pull this rank's image.  Works
-                         with --reduce-out wire (mxfp8, mxfp4).  Same transports and
+                         with --reduce-out wire (mxfp8, mxfp4) and both.  Same transports and
                          exclusions as --reduce-wire
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
@@ -439,12 +444,12 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       }
     } else if (a == "--reduce-out") {
       const std::string v = next();
-      if (v != "bf16" && v != "wire") {
-        std::fprintf(stderr, "p2p_matrix: --reduce-out '%s': bf16 or wire\n", v.c_str());
+      if (v != "bf16" && v != "wire" && v != "both") {
+        std::fprintf(stderr, "p2p_matrix: --reduce-out '%s': bf16, wire or both\n", v.c_str());
         *exit_code = 1;
         return false;
       }
-      cfg->run.reduce_out = v == "wire" ? ReduceOut::Wire : ReduceOut::Bf16;
+      cfg->run.reduce_out = v == "wire" ? ReduceOut::Wire : v == "both" ? ReduceOut::Both : ReduceOut::Bf16;
     } else if (a == "--reduce-own") {
       const std::string v = next();
       if (v != "bf16" && v != "wire") {
@@ -593,16 +598,17 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
       return false;
     }
   }
-  // --reduce-out wire: the requantised output of a --reduce-wire sum, so it
-  // runs where that option runs and beside what it runs beside.  Checked
-  // first: its refusals name this option.
-  if (cfg->run.reduce_out == ReduceOut::Wire) {
+  // --reduce-out wire / both: the requantised output of a --reduce-wire sum, so
+  // it runs where that option runs and beside what it runs beside.  Checked
+  // first: its refusals name this option and the value given.
+  if (cfg->run.reduce_out != ReduceOut::Bf16) {
+    const bool both = cfg->run.reduce_out == ReduceOut::Both;
     std::string why;
     if (cfg->run.reduce != ReduceType::Bf16 || cfg->run.reduce_wire == WireFormat::Off)
       why = "needs --reduce bf16 --reduce-wire FORMAT: the image it stores is the requantised sum of wire images, in their format";
-    if (why.empty() && cfg->run.reduce_wire == WireFormat::Mxfp6)
-      why = "cannot be combined with --reduce-wire mxfp6: 6-bit images are summed to bf16 only, their requantising epilogue "
-            "is not built (mxfp8 and mxfp4 have one)";
+    if (why.empty() && !both && cfg->run.reduce_wire == WireFormat::Mxfp6)
+      why = "cannot be combined with --reduce-wire mxfp6: the 6-bit requantising kernel is reached through --reduce-out both "
+            "(the image and the bf16 it widens to); the image alone is for mxfp8 and mxfp4";
     if (why.empty() && !(cfg->transport == "host" || (cfg->transport == "ipc" && cfg->ipc_engine == "kernel")))
       why = strfmt("needs --transport ipc --ipc-engine kernel (the gfx950 wire-reduce-pack kernel) or --transport host; %s%s%s "
                    "sums no wire images", cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",
@@ -616,7 +622,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
     if (why.empty() && cfg->resume)
       why = "cannot be combined with --resume: the runs in the file are counted by mode, direction and size alone";
     if (!why.empty()) {
-      std::fprintf(stderr, "p2p_matrix: --reduce-out wire %s\n", why.c_str());
+      std::fprintf(stderr, "p2p_matrix: --reduce-out %s %s\n", both ? "both" : "wire", why.c_str());
       *exit_code = 1;
       return false;
     }
@@ -1223,12 +1229,14 @@ int run_app(const AppConfig& cfg, Bootstrap& boot, FILE* out, AppResult* result)
     int most_iters = std::max(cfg.run.iters, cfg.run.warmup);
     if (cfg.iters_auto)
       for (size_t b : cfg.sizes) most_iters = std::max(most_iters, auto_iters(b, cfg.target_bytes));
-    run_cfg.run.gens = verify_generations(*t, boot, max_bytes, slots, most_iters, cfg.run.reduce_own == ReduceOwn::Bf16);
+    run_cfg.run.gens = verify_generations(*t, boot, max_bytes, slots, most_iters,
+                                          (cfg.run.reduce_own == ReduceOwn::Bf16) + (cfg.run.reduce_out == ReduceOut::Both));
   }
   if (const char* rc = std::getenv("P2P_RECHUNK")) run_cfg.run.rechunk = std::atoi(rc) != 0;
   // --reduce-own bf16: a third arena, one own shard per generation (nothing is allocated without the option).
   const size_t send_bytes = slot_stride_bytes(max_bytes) * static_cast<size_t>(run_cfg.run.gens);
-  Buffers bufs(*t, max_bytes, slots * run_cfg.run.gens, send_bytes, cfg.run.reduce_own == ReduceOwn::Bf16 ? send_bytes : 0);
+  Buffers bufs(*t, max_bytes, slots * run_cfg.run.gens, send_bytes, cfg.run.reduce_own == ReduceOwn::Bf16 ? send_bytes : 0,
+               cfg.run.reduce_out == ReduceOut::Both ? send_bytes : 0);
 
   // Connection warm-up outside any timed cell (the reference pays lazy p2p
   // connection setup inside its first cells; --reference keeps that).

@@ -89,10 +89,12 @@ VerifyResult DeviceChecks::verify_unpacked(const void* p, size_t payload_bytes, 
 }
 
 VerifyResult DeviceChecks::verify_wire_reduced(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                               WireFormat fmt, hipStream_t stream, const StreamWait& wait, bool own_bf16) {
+                                               WireFormat fmt, hipStream_t stream, const StreamWait& wait, bool own_bf16,
+                                               bool roundtrip) {
   acc_.reserve(dev::kVerifyShards, [] {});
   dev::launch_verify_reset(acc_.device(), stream);
-  dev::launch_verify_wire_reduced(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, acc_.device(), stream, own_bf16);
+  dev::launch_verify_wire_reduced(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, acc_.device(), stream, own_bf16,
+                                  roundtrip);
   acc_.readback(1, stream);
   wait();
   return verify_result();

@@ -89,8 +89,9 @@ class DeviceChecks {
   // ---- sum of wire images (Transport::verify_reduced_unpacked; kernels.hpp launch_verify_wire_reduced) ----
   // Blocking: reset + the check + finalize + readback.
   // own_bf16: operand 0 (seeds[0]) is the receiver's bf16 shard, not an image.
+  // roundtrip: p is the bf16 output of --reduce-out both.
   VerifyResult verify_wire_reduced(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds, WireFormat fmt,
-                                   hipStream_t stream, const StreamWait& wait, bool own_bf16 = false);
+                                   hipStream_t stream, const StreamWait& wait, bool own_bf16 = false, bool roundtrip = false);
 
   // The requantised sum (Transport::verify_reduced_packed; kernels.hpp launch_verify_wire_reduced_packed).
   VerifyResult verify_wire_reduced_packed(const void* image, size_t payload_bytes, const std::vector<uint64_t>& seeds,

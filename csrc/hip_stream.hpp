@@ -96,9 +96,9 @@ class GpuTransport : public Transport {
   }
 
   VerifyResult verify_reduced_unpacked(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                       WireFormat fmt, bool own_bf16) override {
+                                       WireFormat fmt, bool own_bf16, bool roundtrip) override {
     before_buffer_work();
-    return checks_.verify_wire_reduced(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); }, own_bf16);
+    return checks_.verify_wire_reduced(p, payload_bytes, seeds, fmt, stream_, [this] { sync(); }, own_bf16, roundtrip);
   }
 
   VerifyResult verify_reduced_packed(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,

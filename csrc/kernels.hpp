@@ -236,7 +236,7 @@ void launch_verify_reduced(const void* p, size_t bytes, const uint64_t* seeds, i
 // lane stride), Split sends the wave's 4 KiB through a wave-private LDS slot
 // and stores fully coalesced; Auto is Split.  The same holds for
 // launch_wire_reduce, whose mxfp6 kernel keeps 32 f32 accumulators per lane;
-// launch_wire_reduce_packed has no mxfp6 form and refuses the format.
+// launch_wire_reduce_packed's mxfp6 kernel has store paths of its own (below).
 constexpr int kMaxUnpackOps = 32;
 enum class WireLanes : int { Auto = 0, Contiguous = 1, Split = 2 };
 struct UnpackOp {
@@ -293,6 +293,11 @@ struct WireReduceOp {
   // store stage's LDS slot (wire6_lane.hpp load_block).  OWN is a template
   // parameter beside the fan-in: the all-image kernels are unchanged.
   bool own_bf16 = false;
+  // --reduce-out both (launch_wire_reduce_packed only; launch_wire_reduce wants
+  // it null, a P2P_CHECK): payload_bytes of bf16 in local memory, 16 B aligned,
+  // that receive what the image in dst widens to, wire_unpack of it: every
+  // sum word under wire_roundtrip_word with the block's scale byte.
+  void* dst_bf16 = nullptr;
 };
 void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks = 0,
                         WireLanes lanes = WireLanes::Auto);
@@ -301,8 +306,11 @@ void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stre
 // functions and compares with p word by word; the totals end in acc[0] like
 // launch_verify's (reset acc first).  Never inside timing.
 // own_bf16: operand 0 (seeds[0]) enters as the raw stream.
+// roundtrip: p is the bf16 output of --reduce-out both: after summing, the
+// block's amax of the sums is completed over its 4 lanes and every sum word
+// goes through wire_roundtrip_word (the integer functions) before comparing.
 void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint64_t* seeds, int nseeds, WireFormat fmt,
-                                VerifyAccum* acc, hipStream_t stream, bool own_bf16 = false);
+                                VerifyAccum* acc, hipStream_t stream, bool own_bf16 = false, bool roundtrip = false);
 // payload_bytes of bf16: operand stream `seed` (wire_operand_word over the
 // fill's stream) unquantised, the own shard of a --reduce-own bf16 sum; what
 // launch_fill_packed packs.  The fill kernel's geometry.
@@ -321,16 +329,33 @@ void launch_fill_wire_operand(void* p, size_t payload_bytes, uint64_t seed, hipS
 // two 8 B / 4 B (split) non-temporal stores; the tile's 128 scale bytes and
 // their padding leave as 16 B stores through a double-buffered LDS stage, one
 // barrier per tile.  Same argument rules as launch_wire_reduce; dst is local.
-// Auto is contiguous here, the mapping measured faster in every cell.
+// Auto is contiguous here, the mapping measured faster in every cell, and
+// split when op.dst_bf16 is given: its 8 KiB of bf16 per tile then dominate.
+// op.dst_bf16 non-null (--reduce-out both, the turn-around hop of a two-shot
+// all-reduce): the same launch also stores wire_unpack of that image there, so
+// the owner keeps exactly what its peers will reconstruct; a lane widens its
+// own codes back with the unpack's conversion under the same scale operand and
+// adds two 16 B stores.  Bit-identical to this launch without dst_bf16 followed
+// by launch_multi_unpack of dst.
+// mxfp6 is served by a kernel of its own (wire_reduce_pack6.hip): a lane per
+// block, 256 lanes and two tiles per workgroup, amax, scale byte and the pk32
+// conversions inside the lane, no workgroup barrier; contiguous stores 24 B per
+// lane as three 8 B stores, split sends a wave's 1536 B of codes through its
+// LDS slot and stores coalesced 16 B chunks; Auto is split for mxfp6.
 void launch_wire_reduce_packed(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks = 0,
                                WireLanes lanes = WireLanes::Auto);
+// The mxfp6 kernel behind launch_wire_reduce_packed, which has checked op.
+void launch_wire_reduce_packed6(const WireReduceOp& op, hipStream_t stream, int max_blocks, WireLanes lanes);
 // The check of such an image, in launch_verify_wire_reduced's geometry (one
 // payload vector per lane, 4 lanes per block): regenerates and sums the
 // operand streams, takes the block's amax of the sums, quantises with the
 // integer functions and compares the image's code words and scale byte.  A
 // wrong 32-bit word of codes counts once, a wrong scale byte once; first_bad is
 // the lowest byte offset in the image of either; the checksum sums the code
-// words and the scale bytes; the padding is not read.
+// words and the scale bytes; the padding is not read.  mxfp6: a lane's 8
+// codes are 6 bytes at a 6-byte stride (wire_code_bits6), not whole words; one
+// mismatch is one such 6-byte group with any wrong bit (four groups a block),
+// first_bad its first byte, and the checksum adds the group as a 48-bit number.
 void launch_verify_wire_reduced_packed(const void* image, size_t payload_bytes, const uint64_t* seeds, int nseeds,
                                        WireFormat fmt, VerifyAccum* acc, hipStream_t stream, bool own_bf16 = false);
 

@@ -152,13 +152,17 @@ class Session {
               "reduce_wire needs reduce='bf16' (the format's payload is bf16), no wire, transport 'ipc' / 'ipc:kernel' or "
               "'host', and bytes a multiple of 64");
     // reduce_out="wire": the sum leaves as a wire image in reduce_wire's format (RunConfig::reduce_out).
-    P2P_CHECK(reduce_out.empty() || reduce_out == "bf16" || reduce_out == "wire", "reduce_out '" + reduce_out + "': bf16 or wire");
-    P2P_CHECK(reduce_out != "wire" || (cfg.reduce_wire != WireFormat::Off && !inline_check && diagnose <= 0),
-              "reduce_out='wire' needs reduce='bf16' and reduce_wire (the image's format is the operands'), and neither "
+    // reduce_out="both": that image beside the bf16 it widens to, from one launch; mxfp6 too.
+    P2P_CHECK(reduce_out.empty() || reduce_out == "bf16" || reduce_out == "wire" || reduce_out == "both",
+              "reduce_out '" + reduce_out + "': bf16, wire or both");
+    const bool out_image = reduce_out == "wire" || reduce_out == "both";
+    P2P_CHECK(!out_image || (cfg.reduce_wire != WireFormat::Off && !inline_check && diagnose <= 0),
+              "reduce_out='" + reduce_out + "' needs reduce='bf16' and reduce_wire (the image's format is the operands'), and neither "
               "inline_check nor diagnose");
     P2P_CHECK(reduce_out != "wire" || cfg.reduce_wire != WireFormat::Mxfp6,
-              "reduce_out='wire' with reduce_wire='mxfp6': 6-bit images are summed to bf16 only (mxfp8 and mxfp4 requantise)");
+              "reduce_out='wire' with reduce_wire='mxfp6': the 6-bit requantising kernel is reached through reduce_out='both'");
     if (reduce_out == "wire") cfg.reduce_out = ReduceOut::Wire;
+    if (reduce_out == "both") cfg.reduce_out = ReduceOut::Both;
     // reduce_own="bf16": operand 0 of the sum is the receiver's unquantised shard (RunConfig::reduce_own).
     P2P_CHECK(reduce_own.empty() || reduce_own == "bf16" || reduce_own == "wire", "reduce_own '" + reduce_own + "': bf16 or wire");
     P2P_CHECK(reduce_own != "bf16" || cfg.reduce_wire != WireFormat::Off,
@@ -168,10 +172,11 @@ class Session {
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
-    cfg.gens = verify ? verify_generations(*t_, *boot_, bytes, slots, std::max(iters, warmup), own_shard) : 1;
+    const bool both = cfg.reduce_out == ReduceOut::Both;
+    cfg.gens = verify ? verify_generations(*t_, *boot_, bytes, slots, std::max(iters, warmup), own_shard + both) : 1;
     if (const char* rc = std::getenv("P2P_RECHUNK")) cfg.rechunk = std::atoi(rc) != 0;
     const size_t send_bytes = slot_stride_bytes(bytes) * static_cast<size_t>(cfg.gens);
-    Buffers bufs(*t_, bytes, slots * cfg.gens, send_bytes, own_shard ? send_bytes : 0);
+    Buffers bufs(*t_, bytes, slots * cfg.gens, send_bytes, own_shard ? send_bytes : 0, both ? send_bytes : 0);
     if (warm) {
       warm_connections(*t_, *boot_, s, bufs);
       t_->refine_op_limits(*boot_);
@@ -554,7 +559,7 @@ void device_wire_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_
 }
 
 py::tuple device_verify_wire_reduced(uintptr_t ptr, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                     const std::string& fmt, uintptr_t stream, bool own_bf16) {
+                                     const std::string& fmt, uintptr_t stream, bool own_bf16, bool roundtrip) {
   const WireFormat f = wire_format_arg(fmt);
   wire_payload_arg(payload_bytes);
   DeviceChecks& c = checks_for_current_device();
@@ -562,7 +567,7 @@ py::tuple device_verify_wire_reduced(uintptr_t ptr, size_t payload_bytes, const 
   VerifyResult r;
   {
     py::gil_scoped_release nogil;
-    r = c.verify_wire_reduced(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st), own_bf16);
+    r = c.verify_wire_reduced(reinterpret_cast<const void*>(ptr), payload_bytes, seeds, f, st, stream_wait(st), own_bf16, roundtrip);
   }
   return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
@@ -570,9 +575,10 @@ py::tuple device_verify_wire_reduced(uintptr_t ptr, size_t payload_bytes, const 
 // ---- the same sum, requantised (kernels.hpp launch_wire_reduce_packed) ----
 void device_wire_reduce_packed(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t payload_bytes, const std::string& fmt,
                                uintptr_t stream, const py::object& coherent, int max_blocks, const std::string& lanes,
-                               bool own_bf16) {
+                               bool own_bf16, uintptr_t both) {
   const WireFormat f = wire_format_arg(fmt);
-  const dev::WireReduceOp op = wire_reduce_op_arg(dst, srcs, payload_bytes, coherent, own_bf16, "wire_reduce_packed");
+  dev::WireReduceOp op = wire_reduce_op_arg(dst, srcs, payload_bytes, coherent, own_bf16, "wire_reduce_packed");
+  op.dst_bf16 = reinterpret_cast<void*>(both);
   dev::launch_wire_reduce_packed(op, f, as_stream(stream), max_blocks, wire_lanes_arg(lanes));
 }
 
@@ -1356,9 +1362,10 @@ PYBIND11_MODULE(_p2pcore, m) {
       }, py::arg("ptr"), py::arg("payload_bytes"), py::arg("seed"), py::arg("stream") = 0,
       "Fills payload_bytes at ptr with bf16 operand stream `seed`, unquantised: the own shard of an own_bf16 sum.");
   m.def("verify_wire_reduced", &device_verify_wire_reduced, py::arg("ptr"), py::arg("payload_bytes"), py::arg("seeds"),
-        py::arg("fmt"), py::arg("stream") = 0, py::arg("own_bf16") = false,
+        py::arg("fmt"), py::arg("stream") = 0, py::arg("own_bf16") = false, py::arg("roundtrip") = false,
         "Compares the buffer with the sum of the operand streams `seeds` (operand order), each packed and unpacked: (wrong "
-        "32-bit words, checksum, first bad byte offset or 2**64-1).");
+        "32-bit words, checksum, first bad byte offset or 2**64-1).  roundtrip: the buffer is the bf16 output of wire_reduce_packed's "
+        "`both`, the sum quantised under its block's scale and widened again.");
   m.def("host_wire_reduce", [](const std::vector<py::bytes>& images, size_t payload_bytes, const std::string& fmt, bool own_bf16) {
         const WireFormat f = wire_format_arg(fmt);
         if (images.empty() || images.size() > static_cast<size_t>(kMaxWireReduceSrcs))
@@ -1377,13 +1384,14 @@ PYBIND11_MODULE(_p2pcore, m) {
       "CPU sum of wire images in order as bf16 bytes, bit-compatible with the wire-reduce kernel.");
   m.def("wire_reduce_packed", &device_wire_reduce_packed, py::arg("dst"), py::arg("srcs"), py::arg("payload_bytes"),
         py::arg("fmt"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0, py::arg("lanes") = "auto",
-        py::arg("own_bf16") = false,
-        "The gfx950 wire-reduce-pack kernel: dst = wire_bytes(payload_bytes, fmt) bytes, the wire image in fmt of the bf16 sum "
+        py::arg("own_bf16") = false, py::arg("both") = 0,
+        "The gfx950 wire-reduce-pack kernel ('mxfp8', 'mxfp6' or 'mxfp4'; both: the address of payload_bytes of bf16 that receive, in the same "
+        "launch, what the image widens to, 0 for the image alone): dst = wire_bytes(payload_bytes, fmt) bytes, the wire image in fmt of the bf16 sum "
         "wire_reduce gives for the 1..8 images at srcs, in one launch (coherent: True reads every image in the cross-GPU form; an int, 1 included, is a mask with bit k for "
         "source k, as in wire_reduce, where it used to mean every source; lanes and own_bf16: as wire_reduce).");
   m.def("verify_wire_reduced_packed", &device_verify_wire_reduced_packed, py::arg("ptr"), py::arg("payload_bytes"),
         py::arg("seeds"), py::arg("fmt"), py::arg("stream") = 0, py::arg("own_bf16") = false,
-        "Compares the image with the packed sum of the operand streams `seeds`: (wrong 32-bit code words + wrong scale bytes, "
+        "Compares the image with the packed sum of the operand streams `seeds`: (wrong 32-bit code words (mxfp6: 6-byte groups of 8 codes) + wrong scale bytes, "
         "checksum of code words and scale bytes, first bad byte offset in the image or 2**64-1).");
   m.def("host_wire_reduce_packed", [](const std::vector<py::bytes>& images, size_t payload_bytes, const std::string& fmt,
                                       bool own_bf16) {

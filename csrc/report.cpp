@@ -230,6 +230,7 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
   if (rec.cfg.reduce_wire != WireFormat::Off)
     head.insert(head.size() - 1, strfmt(" reduce-wire=%s", wire_format_name(rec.cfg.reduce_wire)));
   if (rec.cfg.reduce_out == ReduceOut::Wire) head.insert(head.size() - 1, " reduce-out=wire");
+  if (rec.cfg.reduce_out == ReduceOut::Both) head.insert(head.size() - 1, " reduce-out=both");
   if (rec.cfg.reduce_own == ReduceOwn::Bf16) head.insert(head.size() - 1, " reduce-own=bf16");
   std::fprintf(out, "\n== %s ==\n", head.c_str());
   bool blank_diag = rec.mode != Mode::Self && n > 1;
@@ -286,6 +287,10 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
                  static_cast<unsigned long long>(rec.cfg.bytes));
   if (rec.cfg.reduce_out == ReduceOut::Wire)
     std::fprintf(out, "  reduce-out: the sum is requantised in the same launch and stored as a %llu-byte %s image\n",
+                 static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)),
+                 wire_format_name(rec.cfg.reduce_wire));
+  if (rec.cfg.reduce_out == ReduceOut::Both)
+    std::fprintf(out, "  reduce-out: the same launch stores the requantised sum as a %llu-byte %s image and the bf16 it widens to\n",
                  static_cast<unsigned long long>(wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)),
                  wire_format_name(rec.cfg.reduce_wire));
   if (rec.cfg.wire != WireFormat::Off)
@@ -426,9 +431,10 @@ std::string run_to_json(const RunRecord& rec, int n) {
     if (rec.cfg.reduce_wire != WireFormat::Off)  // --reduce-wire: how the operands arrive
       o << ",\"wire\":{\"format\":\"" << wire_format_name(rec.cfg.reduce_wire) << "\",\"payload_bytes\":" << rec.cfg.bytes
         << ",\"wire_bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire) << "}";
-    if (rec.cfg.reduce_out == ReduceOut::Wire)  // --reduce-out wire: what the sum leaves in the slot
+    if (rec.cfg.reduce_out != ReduceOut::Bf16)  // --reduce-out wire / both: the image the sum leaves (both: beside its bf16)
       o << ",\"out\":{\"format\":\"" << wire_format_name(rec.cfg.reduce_wire)
-        << "\",\"bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire) << "}";
+        << "\",\"bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)
+        << (rec.cfg.reduce_out == ReduceOut::Both ? ",\"both\":true}" : "}");
     if (rec.cfg.reduce_own == ReduceOwn::Bf16) o << ",\"own\":\"bf16\"";  // --reduce-own bf16: operand 0 is unquantised
     o << "}";
   }

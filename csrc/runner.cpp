@@ -35,14 +35,14 @@ namespace detail {
 size_t slot_stride(size_t bytes) { return (std::max<size_t>(bytes, 16) + 4095) / 4096 * 4096; }
 }  // namespace detail
 
-Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes, size_t own_bytes)
+Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes, size_t own_bytes, size_t image_bytes)
     : t_(t), cap_(std::max<size_t>(slot_bytes, 16)), send_cap_(std::max(send_bytes, cap_)), stride_(slot_stride(cap_)),
-      nslots_(std::max(recv_slots, 1)), own_cap_(own_bytes) {
+      nslots_(std::max(recv_slots, 1)), own_cap_(own_bytes), image_cap_(image_bytes) {
   // One send buffer + one receive arena: check against free HBM up front so a
   // 288 GB sweep fails with an explanation instead of a hipMalloc error mid-run.
   size_t free_b = 0, total_b = 0;
   const double arena = static_cast<double>(stride_) * static_cast<double>(nslots_);
-  const double need = static_cast<double>(send_cap_) + arena + static_cast<double>(own_cap_);
+  const double need = static_cast<double>(send_cap_) + arena + static_cast<double>(own_cap_) + static_cast<double>(image_cap_);
   if (t_.mem_info(&free_b, &total_b) && need > 0.98 * static_cast<double>(free_b))
     P2P_FATAL(strfmt("buffers need %.2f GiB (send %s + %d receive slots of %s) but only %.2f of %.2f GiB are free on "
                      "this GPU; use a smaller --size/--sizes maximum or a mode with fewer concurrent peers",
@@ -51,6 +51,7 @@ Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_by
   send_ = t_.alloc(send_cap_);
   recv_ = t_.alloc(stride_ * static_cast<size_t>(nslots_));
   if (own_cap_) own_ = t_.alloc(own_cap_);  // local operands only: not part of the registered set
+  if (image_cap_) image_ = t_.alloc(image_cap_);  // local outputs only: not registered either
   Transport::BufferSet set;
   set.send = send_;
   set.send_bytes = send_cap_;
@@ -67,6 +68,7 @@ Buffers::~Buffers() {
   // on, so the first error is the one that surfaces.
   try {
     t_.unregister_buffers(send_);
+    if (image_) t_.release(image_);
     if (own_) t_.release(own_);
     if (recv_) t_.release(recv_);
     if (send_) t_.release(send_);
@@ -161,7 +163,11 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
   const bool own_bf16 = reduce_own == ReduceOwn::Bf16;
   P2P_CHECK(!own_bf16 || off + bytes <= bufs.own_capacity(), "reduce_own bf16: the buffers hold no own shard for this generation");
   const void* own = own_bf16 ? bufs.own_at(off) : bufs.send_at(off);
-  if (reduce_wire != WireFormat::Off && reduce_out == ReduceOut::Wire && !ops.recv_from.empty())
+  if (reduce_wire != WireFormat::Off && reduce_out == ReduceOut::Both && !ops.recv_from.empty()) {
+    // The slot takes the bf16 round trip, the generation's region of the image arena the image.
+    P2P_CHECK(off + wire_bytes(bytes, reduce_wire) <= bufs.image_capacity(), "reduce_out both: the buffers hold no image region for this generation");
+    t.reduce_packed_from(bufs.recv_buf(base), bytes, own, ops.recv_from, off, reduce_wire, own_bf16, bufs.image_at(off));
+  } else if (reduce_wire != WireFormat::Off && reduce_out == ReduceOut::Wire && !ops.recv_from.empty())
     t.reduce_packed_from(bufs.recv_buf(base), bytes, own, ops.recv_from, off, reduce_wire, own_bf16);
   else if (reduce_wire != WireFormat::Off && !ops.recv_from.empty())
     t.reduce_unpacked_from(bufs.recv_buf(base), bytes, own, ops.recv_from, off, reduce_wire, own_bf16);
@@ -198,9 +204,9 @@ size_t shared_free_budget(Transport& t, Bootstrap& boot, size_t fallback, size_t
   return budget;
 }
 
-int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters, bool own_shard) {
-  // One generation = a send region + `slots` receive slots (+ a region of the own arena).
-  const size_t per_gen = slot_stride(max_bytes) * static_cast<size_t>(std::max(1, slots) + 1 + (own_shard ? 1 : 0));
+int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters, int extra_arenas) {
+  // One generation = a send region + `slots` receive slots (+ a region of the own arena, + one of the image arena).
+  const size_t per_gen = slot_stride(max_bytes) * static_cast<size_t>(std::max(1, slots) + 1 + std::max(0, extra_arenas));
   size_t budget = shared_free_budget(t, boot, size_t{256} << 20, size_t{32} << 30);
   if (const char* b = std::getenv("P2P_VERIFY_BUDGET")) budget = parse_size(b);
   long g = std::max(1, iters);
@@ -264,6 +270,12 @@ void prepare_payload(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
       t.fill(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
              generation_seed(t.rank(), cfg.bytes, cfg.salt, g));
   if (cfg.verify) zero_slots(t, phase, cfg, bufs, gens);
+  // --reduce-out both: the image regions are poisoned like the slots, so a launch that never ran shows in both checks.
+  if (cfg.verify && cfg.reduce_out == ReduceOut::Both && !ops.recv_from.empty()) {
+    const size_t span = slot_stride(cfg.bytes) * static_cast<size_t>(gens - 1) + wire_bytes(cfg.bytes, cfg.reduce_wire);
+    P2P_CHECK(span <= bufs.image_capacity(), "reduce_out both: the buffers hold no image region for this generation");
+    t.zero(bufs.image_at(0), span);
+  }
 }
 
 // Wrong words in this rank's receive slots of generations [0, gens);
@@ -280,11 +292,16 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
       std::vector<uint64_t> seeds{generation_seed(t.rank(), cfg.bytes, cfg.salt, g)};
       for (int peer : ops.recv_from) seeds.push_back(generation_seed(peer, cfg.bytes, cfg.salt, g));
       const bool own_bf16 = cfg.reduce_own == ReduceOwn::Bf16;
-      const VerifyResult v = cfg.reduce_out == ReduceOut::Wire
+      VerifyResult v = cfg.reduce_out == ReduceOut::Wire
                                  ? t.verify_reduced_packed(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire, own_bf16)
+                                 : cfg.reduce_out == ReduceOut::Both
+                                 ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire, own_bf16, true)
                                  : cfg.reduce_wire != WireFormat::Off
                                  ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire, own_bf16)
                                  : t.verify_reduced(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce);
+      if (cfg.reduce_out == ReduceOut::Both)  // and the image beside it: the two outputs' mismatches add up
+        v.mismatches += t.verify_reduced_packed(bufs.image_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes, seeds,
+                                                cfg.reduce_wire, own_bf16).mismatches;
       bad += v.mismatches;
       if (per_job)
         for (size_t i = 0; i < ops.recv_from.size(); ++i) per_job->push_back(i ? 0 : v.mismatches);
@@ -649,11 +666,11 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
                        "(its own image and 7 incoming)", r.recv_from.size()));
   }
   P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Off,
-            "reduce_out wire: only with reduce_wire (the image's format is the operands')");
+            "reduce_out wire / both: only with reduce_wire (the image's format is the operands')");
   P2P_CHECK(cfg.reduce_own == ReduceOwn::Wire || cfg.reduce_wire != WireFormat::Off,
             "reduce_own bf16: only with reduce_wire (it says what operand 0 of that sum is)");
-  P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Mxfp6,
-            "reduce_out wire: not with reduce_wire mxfp6 (6-bit images are summed to bf16 only)");
+  P2P_CHECK(cfg.reduce_out != ReduceOut::Wire || cfg.reduce_wire != WireFormat::Mxfp6,
+            "reduce_out wire: not with reduce_wire mxfp6 (reduce_out both serves 6-bit images)");
   if (cfg.wire != WireFormat::Off) {
     P2P_CHECK(t.supports_wire(), "wire: this transport cannot unpack a wire image (ipc with the kernel engine, or host)");
     P2P_CHECK(cfg.bytes % kWireBlockBytes == 0, "wire: the message size must be a multiple of 64");

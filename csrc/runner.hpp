@@ -33,7 +33,7 @@ enum class Timing { Events, Wallclock };
 const char* timing_name(Timing t);
 Timing parse_timing(const std::string& s);
 
-enum class ReduceOut : int { Bf16 = 0, Wire = 1 };
+enum class ReduceOut : int { Bf16 = 0, Wire = 1, Both = 2 };
 enum class ReduceOwn : int { Wire = 0, Bf16 = 1 };
 
 struct RunConfig {
@@ -105,7 +105,13 @@ struct RunConfig {
   // an image in the operands' format that the next hop of a quantised ring
   // could forward (transport.hpp reduce_packed_from), checked against the
   // packed sum of the operand streams.  Flows are still timed and reported in
-  // payload bytes.  Wire needs reduce_wire.
+  // payload bytes.  Wire needs reduce_wire.  Both: the turn-around hop of a
+  // two-shot quantised all-reduce: the same launch stores that image (into the
+  // image arena of the buffers, Buffers::image_at, one region per generation)
+  // and, in the receive slot, the bf16 it widens to: what the peers that pull
+  // the image will reconstruct, so every rank ends with the same values.  Both
+  // outputs are checked.  Both needs reduce_wire too; unlike Wire it takes
+  // mxfp6.
   ReduceOut reduce_out = ReduceOut::Bf16;
   // What operand 0 of a reduce_wire sum is (--reduce-own).  Wire: the
   // receiver's own image, as above.  Bf16: the receiver's own shard as a real
@@ -225,8 +231,10 @@ class Buffers {
   // `slot_bytes` per receive slot; the send buffer holds `send_bytes`
   // (default: one message).  own_bytes > 0 adds a third arena of that size
   // (RunConfig::reduce_own = Bf16: one slot_stride per generation), local
-  // memory that no peer reads: it is not registered.
-  Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes = 0, size_t own_bytes = 0);
+  // memory that no peer reads: it is not registered.  image_bytes > 0 adds a
+  // fourth of the same shape (RunConfig::reduce_out = Both: where a
+  // generation's requantised sum goes while the receive slot takes its bf16).
+  Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes = 0, size_t own_bytes = 0, size_t image_bytes = 0);
   ~Buffers();
   Buffers(const Buffers&) = delete;
   Buffers& operator=(const Buffers&) = delete;
@@ -234,6 +242,8 @@ class Buffers {
   void* send_at(size_t offset) const { return static_cast<char*>(send_) + offset; }
   void* own_at(size_t offset) const { return own_ ? static_cast<char*>(own_) + offset : nullptr; }
   size_t own_capacity() const { return own_cap_; }
+  void* image_at(size_t offset) const { return image_ ? static_cast<char*>(image_) + offset : nullptr; }
+  size_t image_capacity() const { return image_cap_; }
   void* recv_buf(int slot) const;
   void* recv_base() const { return recv_; }
   size_t capacity() const { return cap_; }          // bytes per receive slot
@@ -251,6 +261,8 @@ class Buffers {
   void* recv_ = nullptr;
   size_t own_cap_ = 0;
   void* own_ = nullptr;
+  size_t image_cap_ = 0;
+  void* image_ = nullptr;
 };
 
 // Receive slot on `peer` that holds messages from `me` in `phase` (position
@@ -286,9 +298,10 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
 // `slots` receive slots per iteration and up to `iters` iterations: as many as
 // P2P_VERIFY_BUDGET bytes of send regions + receive slots allow (default a
 // quarter of free device memory, at most 32 GiB; 256 MiB where the transport
-// cannot tell), agreed by every rank (collective).  own_shard: a generation
-// also holds a region of the own arena (RunConfig::reduce_own = Bf16).
-int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters, bool own_shard = false);
+// cannot tell), agreed by every rank (collective).  extra_arenas: how many
+// further regions a generation holds, one of the own arena
+// (RunConfig::reduce_own = Bf16) and one of the image arena (reduce_out = Both).
+int verify_generations(Transport& t, Bootstrap& boot, size_t max_bytes, int slots, int iters, int extra_arenas = 0);
 // Collective: a quarter of this rank's GPU's free memory (at most `cap`;
 // `fallback` where the transport cannot tell), divided between the ranks that
 // share the GPU (Transport::device_key).  Every rank drains its stream and

@@ -180,9 +180,10 @@ class Transport {
   virtual void reduce_unpacked_from(void* /*dst*/, size_t /*payload_bytes*/, const void* /*local_image*/,
                                     const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/,
                                     bool /*own_bf16*/ = false) {}
+  // roundtrip: p is the bf16 output of reduce_packed_from with image_dst.
   virtual VerifyResult verify_reduced_unpacked(const void* /*p*/, size_t /*payload_bytes*/,
                                                const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/,
-                                               bool /*own_bf16*/ = false) {
+                                               bool /*own_bf16*/ = false, bool /*roundtrip*/ = false) {
     return {};
   }
   // The same hop with a requantised output (--reduce-out wire): dst receives
@@ -193,9 +194,13 @@ class Transport {
   //   verify_reduced_packed  blocking: the image at p against the packed sum
   //                          of the operand streams; a wrong 32-bit word of
   //                          element codes and a wrong scale byte count once.
+  // image_dst (--reduce-out both, the turn-around hop of a two-shot
+  // all-reduce): local memory of wire_bytes(payload_bytes), 16 B aligned,
+  // registered or not, receives that image, and dst, still a registered slot,
+  // the payload_bytes of bf16 the image widens to, from the same launch.
   virtual void reduce_packed_from(void* /*dst*/, size_t /*payload_bytes*/, const void* /*local_image*/,
                                   const std::vector<int>& /*peers*/, size_t /*src_offset*/, WireFormat /*fmt*/,
-                                  bool /*own_bf16*/ = false) {}
+                                  bool /*own_bf16*/ = false, void* /*image_dst*/ = nullptr) {}
   virtual VerifyResult verify_reduced_packed(const void* /*p*/, size_t /*payload_bytes*/,
                                              const std::vector<uint64_t>& /*seeds*/, WireFormat /*fmt*/,
                                              bool /*own_bf16*/ = false) {

@@ -219,7 +219,8 @@ void host_fill_wire_operand(void* p, size_t n, uint64_t seed) {
   }
 }
 
-VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f, bool own_bf16) {
+VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f, bool own_bf16,
+                                      bool roundtrip) {
   check_wire(n, f, "host_verify_wire_reduced");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "host_verify_wire_reduced: 1..8 operand seeds");
   VerifyResult r;
@@ -232,12 +233,20 @@ VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* s
       for (uint32_t i = 0; i < kWireBlockElems; ++i) amax = std::max<uint32_t>(amax, x[j][i] & 0x7FFFu);
       sb[j] = wire_scale_byte(amax, f);
     }
+    uint32_t want[16], amax = 0;
     for (uint32_t i = 0; i < 16; ++i) {
-      uint32_t w[kMaxWireReduceSrcs], got;
+      uint32_t w[kMaxWireReduceSrcs];
       for (int j = 0; j < nseeds; ++j) w[j] = x[j][2 * i] | static_cast<uint32_t>(x[j][2 * i + 1]) << 16;
+      want[i] = wire_reduce_word(w, sb, nseeds, f, own_bf16);
+      amax = std::max(amax, wire_word_amax(want[i]));
+    }
+    // --reduce-out both: what the block's image widens to.
+    for (uint32_t i = 0; roundtrip && i < 16; ++i) want[i] = wire_roundtrip_word(want[i], wire_scale_byte(amax, f), f);
+    for (uint32_t i = 0; i < 16; ++i) {
+      uint32_t got;
       std::memcpy(&got, static_cast<const char*>(p) + at + 4 * i, 4);
       r.checksum += got;
-      if (got != wire_reduce_word(w, sb, nseeds, f, own_bf16)) {
+      if (got != want[i]) {
         if (!r.mismatches) r.first_bad = at + 4 * i;
         ++r.mismatches;
       }
@@ -249,7 +258,6 @@ VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* s
 // ---- the same sum, requantised (wire_reduce_op.hpp) ----
 void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f, bool own_bf16) {
   check_wire(n, f, "host_wire_reduce_packed");
-  P2P_CHECK(f != WireFormat::Mxfp6, "host_wire_reduce_packed: mxfp6 images are summed to bf16 only (no requantised output yet)");
   std::vector<char> sum(n);
   host_wire_reduce(sum.data(), images, k, n, f, own_bf16);
   host_wire_pack(out_image, sum.data(), n, f);
@@ -258,7 +266,6 @@ void host_wire_reduce_packed(void* out_image, const void* const* images, int k, 
 VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f,
                                              bool own_bf16) {
   check_wire(n, f, "host_verify_wire_reduced_packed");
-  P2P_CHECK(f != WireFormat::Mxfp6, "host_verify_wire_reduced_packed: mxfp6 images are summed to bf16 only (no requantised output yet)");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "host_verify_wire_reduced_packed: 1..8 operand seeds");
   const auto* in = static_cast<const uint8_t*>(image);
   const uint32_t code_words = wire_block_elem_bytes(f) / 4, per = 16 / code_words;  // sum words per word of codes
@@ -283,7 +290,13 @@ VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const 
       amax = std::max(amax, wire_word_amax(sum[i]));
     }
     const uint32_t out_sb = wire_scale_byte(amax, f);
-    for (uint32_t c = 0; c < code_words; ++c) {
+    for (uint32_t c = 0; f == WireFormat::Mxfp6 && c < 4; ++c) {  // 6-byte groups of 8 codes, not whole words
+      uint64_t got = 0;
+      std::memcpy(&got, in + elems + 6 * c, 6);
+      r.checksum += got;
+      if (got != wire_code_bits6(sum + 4 * c, out_sb)) wrong(elems + 6 * c);
+    }
+    for (uint32_t c = 0; f != WireFormat::Mxfp6 && c < code_words; ++c) {
       uint32_t got;
       std::memcpy(&got, in + elems + 4 * c, 4);
       r.checksum += got;
@@ -433,8 +446,8 @@ class HostTransport final : public Transport {
   bool supports_reduce_wire() const override { return true; }
   void fill_wire_operand(void* p, size_t payload_bytes, uint64_t seed) override { host_fill_wire_operand(p, payload_bytes, seed); }
   VerifyResult verify_reduced_unpacked(const void* p, size_t payload_bytes, const std::vector<uint64_t>& seeds,
-                                       WireFormat fmt, bool own_bf16) override {
-    return host_verify_wire_reduced(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, own_bf16);
+                                       WireFormat fmt, bool own_bf16, bool roundtrip) override {
+    return host_verify_wire_reduced(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, own_bf16, roundtrip);
   }
   void reduce_unpacked_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers, size_t,
                             WireFormat fmt, bool own_bf16) override {
@@ -455,9 +468,10 @@ class HostTransport final : public Transport {
     return host_verify_wire_reduced_packed(p, payload_bytes, seeds.data(), static_cast<int>(seeds.size()), fmt, own_bf16);
   }
   void reduce_packed_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
-                          size_t src_offset, WireFormat fmt, bool own_bf16) override {
+                          size_t src_offset, WireFormat fmt, bool own_bf16, void* image_dst) override {
     reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt, own_bf16);
     wire_reduce_.packed = true;
+    wire_reduce_.image_dst = image_dst;
   }
 
   void group_begin() override {
@@ -498,8 +512,11 @@ class HostTransport final : public Transport {
       const size_t image = wire_bytes(wire_reduce_.bytes, wire_reduce_.fmt);
       std::vector<const void*> images{wire_reduce_.local_image};
       for (size_t i = 0; i < wire_reduce_.npeers; ++i) images.push_back(scratch_.data() + i * image);
-      (wire_reduce_.packed ? host_wire_reduce_packed : host_wire_reduce)(wire_reduce_.dst, images.data(), static_cast<int>(images.size()),
+      void* out = wire_reduce_.image_dst ? wire_reduce_.image_dst : wire_reduce_.dst;
+      (wire_reduce_.packed ? host_wire_reduce_packed : host_wire_reduce)(out, images.data(), static_cast<int>(images.size()),
                                                                          wire_reduce_.bytes, wire_reduce_.fmt, wire_reduce_.own_bf16);
+      // --reduce-out both: the slot keeps what the image widens to.
+      if (wire_reduce_.image_dst) host_wire_unpack(wire_reduce_.dst, wire_reduce_.image_dst, wire_reduce_.bytes, wire_reduce_.fmt);
     }
     wire_reduce_ = {};
     // Injected skip fault: the images were read off the wire and are dropped.
@@ -532,6 +549,7 @@ class HostTransport final : public Transport {
     size_t npeers = 0;
     bool packed = false;  // reduce_packed_from: dst receives the sum's wire image
     bool own_bf16 = false;  // local_image is the own shard in bf16
+    void* image_dst = nullptr;  // --reduce-out both: the image goes here, dst takes its unpack
   };
   struct PendingUnpack {
     void* dst;

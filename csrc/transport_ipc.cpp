@@ -346,10 +346,15 @@ class IpcTransport final : public GpuTransport {
   }
   // --reduce-out wire: the same op, launched as the wire-reduce-pack kernel
   // (kernels.hpp launch_wire_reduce_packed): dst receives the sum's image.
+  // image_dst (--reduce-out both): the image goes there and dst takes its bf16 round trip, still one launch.
   void reduce_packed_from(void* dst, size_t payload_bytes, const void* local_image, const std::vector<int>& peers,
-                          size_t src_offset, WireFormat fmt, bool own_bf16) override {
+                          size_t src_offset, WireFormat fmt, bool own_bf16, void* image_dst) override {
     reduce_unpacked_from(dst, payload_bytes, local_image, peers, src_offset, fmt, own_bf16);
     wire_reduce_packed_ = true;
+    if (image_dst && wire_reduce_.dst) {  // not posted under an injected skip fault
+      wire_reduce_.dst_bf16 = dst;
+      wire_reduce_.dst = image_dst;
+    }
   }
 
   void group_end() override {

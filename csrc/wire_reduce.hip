@@ -325,7 +325,8 @@ struct Partial {
 };
 
 // verify_unpacked_kernel's geometry: one 16 B vector per lane, 4 lanes per block.
-template <WireFormat F>
+// RT: the expected word is the sum's round trip under its block's scale byte (--reduce-out both).
+template <WireFormat F, bool RT>
 __global__ __launch_bounds__(kBlock) void verify_wire_reduced_kernel(const uint4* __restrict__ p, uint64_t nvec,
                                                                      const SeedArgs s, VerifyAccum* __restrict__ out) {
   Partial acc{0, 0, ~0ull};
@@ -352,11 +353,24 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_kernel(const uint4
         else reduce_add(sum[c], x, ReduceType::Bf16);
       }
     }
+    uint32_t want[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) want[c] = reduce_finish(sum[c], ReduceType::Bf16);
+    if constexpr (RT) {  // every lane takes part in the shuffles
+      uint32_t amax = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) amax = max(amax, wire_word_amax(want[c]));
+      amax = max(amax, static_cast<uint32_t>(__shfl_xor(static_cast<int>(amax), 1, 64)));
+      amax = max(amax, static_cast<uint32_t>(__shfl_xor(static_cast<int>(amax), 2, 64)));
+      const uint32_t sb = wire_scale_byte(amax, F);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) want[c] = wire_roundtrip_word(want[c], sb, F);
+    }
     if (in) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         acc.sum += v[c];
-        if (v[c] != reduce_finish(sum[c], ReduceType::Bf16)) {
+        if (v[c] != want[c]) {
           acc.mism += 1;
           acc.first = min(acc.first, static_cast<unsigned long long>(i * 16 + 4 * c));
         }
@@ -444,6 +458,7 @@ void launch_wire_reduce_f(bool split, bool own, int nsrc, uint32_t grid, const W
 void launch_wire_reduce(const WireReduceOp& op, WireFormat fmt, hipStream_t stream, int max_blocks, WireLanes lanes) {
   check_format(fmt, op.payload_bytes, "wire_reduce");
   P2P_CHECK(op.nsrc >= 1 && op.nsrc <= kMaxWireReduceSrcs, "wire_reduce: an op needs 1..8 sources");
+  P2P_CHECK(!op.dst_bf16, "wire_reduce: dst_bf16 belongs to wire_reduce_packed (the bf16 sum is dst here)");
   P2P_CHECK(!op.own_bf16 || !(op.coherent_mask & 1u), "wire_reduce: a bf16 own shard (source 0) is local memory, not a peer's buffer");
   if (!op.payload_bytes) return;
   P2P_CHECK(op.dst && reinterpret_cast<uintptr_t>(op.dst) % 16 == 0, "wire_reduce: 16-byte aligned buffers required");
@@ -478,7 +493,7 @@ void launch_fill_wire_operand(void* p, size_t payload_bytes, uint64_t seed, hipS
 }
 
 void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint64_t* seeds, int nseeds, WireFormat fmt,
-                                VerifyAccum* acc, hipStream_t stream, bool own_bf16) {
+                                VerifyAccum* acc, hipStream_t stream, bool own_bf16, bool roundtrip) {
   check_format(fmt, payload_bytes, "verify_wire_reduced");
   P2P_CHECK(nseeds >= 1 && nseeds <= kMaxWireReduceSrcs, "verify_wire_reduced: 1..8 operand seeds");
   if (payload_bytes) {
@@ -491,12 +506,13 @@ void launch_verify_wire_reduced(const void* p, size_t payload_bytes, const uint6
     const uint64_t cap = static_cast<uint64_t>(cu_count()) * kVerifyPerCu;
     const unsigned grid = static_cast<unsigned>(std::max<uint64_t>(1, std::min((nvec + kBlock - 1) / kBlock, cap)));
     const auto* vp = static_cast<const uint4*>(p);
+    auto launch = [&](auto kernel) { kernel<<<grid, kBlock, 0, stream>>>(vp, nvec, s, acc); };
     if (fmt == WireFormat::Mxfp8)
-      verify_wire_reduced_kernel<WireFormat::Mxfp8><<<grid, kBlock, 0, stream>>>(vp, nvec, s, acc);
+      roundtrip ? launch(verify_wire_reduced_kernel<WireFormat::Mxfp8, true>) : launch(verify_wire_reduced_kernel<WireFormat::Mxfp8, false>);
     else if (fmt == WireFormat::Mxfp6)
-      verify_wire_reduced_kernel<WireFormat::Mxfp6><<<grid, kBlock, 0, stream>>>(vp, nvec, s, acc);
+      roundtrip ? launch(verify_wire_reduced_kernel<WireFormat::Mxfp6, true>) : launch(verify_wire_reduced_kernel<WireFormat::Mxfp6, false>);
     else
-      verify_wire_reduced_kernel<WireFormat::Mxfp4><<<grid, kBlock, 0, stream>>>(vp, nvec, s, acc);
+      roundtrip ? launch(verify_wire_reduced_kernel<WireFormat::Mxfp4, true>) : launch(verify_wire_reduced_kernel<WireFormat::Mxfp4, false>);
     HIPCHECK(hipGetLastError());
   }
   // The finalize of launch_verify (zero bytes: nothing else runs): shards -> acc[0].

@@ -69,7 +69,15 @@
 // to large ones, so the format's subnormals and zeros get more frequent under
 // the block's scale; wire_quantize covers those (its contract asks only for a
 // zero or normal bf16 and a quotient inside the format, which the no-clip
-// scale guarantees).
+// scale guarantees).  mxfp6 (e2m3): the sum's range is the one argued above,
+// bf16 exponent fields in about [47, 121], and e2m3's scale-byte rule is E - 2
+// (significand <= 1.875) or E - 1, so the byte lies within [45, 120] and the
+// clamp never acts here either.  A -0 sum gives the code 0x20, which widens
+// back to -0 under any scale byte.
+//
+// Both outputs (--reduce-out both).  The bf16 output beside that image is
+// wire_unpack of it: wire_roundtrip_word of every sum word under the block's
+// scale byte.  Unpacking is exact (wire_op.hpp), so nothing is rounded again.
 #pragma once
 
 #include <cstddef>
@@ -99,9 +107,11 @@ P2P_HD uint32_t wire_reduce_word(const uint32_t* w, const uint32_t* sb, int k, W
 void host_wire_reduce(void* out, const void* const* images, int k, size_t n, WireFormat f, bool own_bf16 = false);
 // Compares p with the sum of the operand streams `seeds` (operand order), each
 // packed and unpacked by the shared functions (own_bf16: all but the first); a
-// wrong 32-bit word counts once.
+// wrong 32-bit word counts once.  roundtrip: p is the bf16 output of
+// --reduce-out both, the sum's words under wire_roundtrip_word with the scale
+// byte of the block's sums.
 VerifyResult host_verify_wire_reduced(const void* p, size_t n, const uint64_t* seeds, int nseeds, WireFormat f,
-                                      bool own_bf16 = false);
+                                      bool own_bf16 = false, bool roundtrip = false);
 // n bytes of bf16: operand stream `seed` as a receiver holds its own shard.
 void host_fill_wire_operand(void* p, size_t n, uint64_t seed);
 
@@ -120,13 +130,24 @@ P2P_HD uint32_t wire_code_word(const uint32_t* w, uint32_t sb, WireFormat f) {
     out |= (wire_quantize(w[i] & 0xFFFFu, sb, f) | (wire_quantize(w[i] >> 16, sb, f) << bits)) << (2 * bits * i);
   return out;
 }
+// mxfp6: the codes of four sum words (8 elements) under the block's scale byte,
+// 48 bits = the 6 bytes they occupy in the block's 24, element 0 lowest.
+P2P_HD uint64_t wire_code_bits6(const uint32_t* w, uint32_t sb) {
+  uint64_t out = 0;
+  for (int i = 0; i < 4; ++i) {
+    const uint64_t lo = wire_quantize(w[i] & 0xFFFFu, sb, WireFormat::Mxfp6), hi = wire_quantize(w[i] >> 16, sb, WireFormat::Mxfp6);
+    out |= (lo | (hi << 6)) << (12 * i);
+  }
+  return out;
+}
 // out_image: wire_bytes(n, f) bytes = the wire image (padding zeroed) of the
 // sum host_wire_reduce gives for the k images.  Any alignment.
 void host_wire_reduce_packed(void* out_image, const void* const* images, int k, size_t n, WireFormat f, bool own_bf16 = false);
 // Compares `image` with the packed sum of the operand streams `seeds`: a wrong
 // 32-bit word of element codes counts once, a wrong scale byte once, first_bad
 // is the lowest byte offset in the image of either, the checksum is the sum
-// of the code words and the scale bytes.  The padding is not read.
+// of the code words and the scale bytes.  The padding is not read.  mxfp6: the
+// unit is the 6 bytes of 8 codes (wire_code_bits6), four a block.
 VerifyResult host_verify_wire_reduced_packed(const void* image, size_t n, const uint64_t* seeds, int nseeds, WireFormat f,
                                              bool own_bf16 = false);
 

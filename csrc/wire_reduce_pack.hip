@@ -36,6 +36,15 @@
 //     tile i's stage have returned.
 //   * Lanes past a ragged tile's end take part in every shuffle and barrier
 //     and store nothing; a block's lanes are all in or all out.
+//   * BOTH (WireReduceOp::dst_bf16, --reduce-out both): the turn-around hop of
+//     a two-shot all-reduce keeps what its peers will reconstruct from the
+//     image.  A further template parameter, so the image-only kernels are
+//     what they were: after narrow8 the lane widens its own codes back with
+//     v_cvt_scalef32_pk_bf16_fp8 / _fp4 under the same byte << 23 (the unpack's
+//     conversion) and stores its 16 bf16 as two 16 B non-temporal stores
+//     (split: 4 KiB apart, both coalesced; contiguous: the lane's 32 B).
+//   * mxfp6 has a kernel of its own, a lane per block and no barrier:
+//     wire_reduce_pack6.hip.  Its check is here with the others'.
 //   * No packed f32 instructions in this object (Makefile).
 #include <hip/hip_runtime.h>
 
@@ -73,6 +82,7 @@ struct ReducePackArgs {
   uint64_t ntiles;
   uint32_t last_blocks;  // blocks of the last tile, 1..128
   uint32_t coherent;     // WireReduceOp::coherent_mask
+  char* dst_bf16;        // BOTH: the round trip of the image, payload bytes of bf16
 };
 
 __device__ __forceinline__ float scale_operand(uint32_t sb) { return __builtin_bit_cast(float, sb << 23); }
@@ -129,6 +139,26 @@ __device__ __forceinline__ void narrow8(const uint32_t (&h)[4], uint32_t sb, uin
   }
 }
 
+// BOTH: the codes narrow8 gave, widened again under the same scale byte: 8 bf16.
+template <WireFormat F>
+__device__ __forceinline__ u32x4 widen_back8(const uint32_t* c, uint32_t sb) {
+  const float scale = scale_operand(sb);
+  bf16x2 r[4];
+  if constexpr (F == WireFormat::Mxfp8) {
+    r[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], scale, false);
+    r[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], scale, true);
+    r[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], scale, false);
+    r[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], scale, true);
+  } else {
+    r[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c[0], scale, 0);
+    r[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c[0], scale, 1);
+    r[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c[0], scale, 2);
+    r[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c[0], scale, 3);
+  }
+  return u32x4{__builtin_bit_cast(uint32_t, r[0]), __builtin_bit_cast(uint32_t, r[1]), __builtin_bit_cast(uint32_t, r[2]),
+               __builtin_bit_cast(uint32_t, r[3])};
+}
+
 // max with the lane at (lane ^ MASK), MASK 1 or 2: both stay inside a quad, so
 // a DPP quad_perm ([1,0,3,2] / [2,3,0,1]) on the v_max does it without the
 // LDS crossbar a general shuffle goes through.  Every lane is active here.
@@ -166,7 +196,8 @@ using wire_own::load_own;  // the own shard's load side: wire_own_lane.hpp
 using wire_own::widen_own;
 
 // OWN: source 0 is the receiver's own shard in bf16 (local memory), not an image.
-template <WireFormat F, int K, bool SPLIT, bool OWN>
+// BOTH: dst_bf16 receives the image's round trip beside it.
+template <WireFormat F, int K, bool SPLIT, bool OWN, bool BOTH>
 __global__ __launch_bounds__(kBlock) void wire_reduce_pack_kernel(const ReducePackArgs a) {
   constexpr uint32_t EB = wire_block_elem_bytes(F);
   constexpr uint32_t kFullTile = wire_tile_bytes(kWireTileBlocks, F);
@@ -276,6 +307,11 @@ __global__ __launch_bounds__(kBlock) void wire_reduce_pack_kernel(const ReducePa
       if (in0) __builtin_nontemporal_store(n0[0], reinterpret_cast<uint32_t*>(wt + c0));
       if (in1) __builtin_nontemporal_store(n1[0], reinterpret_cast<uint32_t*>(wt + c1));
     }
+    if constexpr (BOTH) {
+      char* pd = a.dst_bf16 + t * kWireTilePayload;
+      if (in0) __builtin_nontemporal_store(widen_back8<F>(n0, sb0), reinterpret_cast<u32x4*>(pd + 2 * e0));
+      if (in1) __builtin_nontemporal_store(widen_back8<F>(n1, sb1), reinterpret_cast<u32x4*>(pd + 2 * e1));
+    }
     // The tile's scale bytes and the zero padding behind them, through this
     // tile's half of the LDS stage (blk0, blk1 < 128 for every lane).
     if (first_of_block) {
@@ -346,17 +382,28 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_packed_kernel(cons
       const uint32_t iv = static_cast<uint32_t>(i % kTileVecs);
       const uint32_t nb = t + 1 == ntiles ? last_blocks : kWireTileBlocks;
       const uint64_t at = t * kFullTile + iv * (EB / 4);
-#pragma unroll
-      for (int c = 0; c < CW; ++c) {
-        const uint32_t got = *reinterpret_cast<const uint32_t*>(image + at + 4 * c);
+      if constexpr (F == WireFormat::Mxfp6) {
+        // The lane's 8 codes are 6 bytes at a 6-byte stride, 2 B aligned: one unit of the count.
+        const auto* q = reinterpret_cast<const uint16_t*>(image + at);
+        const unsigned long long got = q[0] | static_cast<unsigned long long>(q[1]) << 16 | static_cast<unsigned long long>(q[2]) << 32;
         acc.sum += got;
-        if (got != wire_code_word(h + (4 / CW) * c, sb, F)) {
+        if (got != wire_code_bits6(h, sb)) {
           acc.mism += 1;
-          acc.first = min(acc.first, static_cast<unsigned long long>(at + 4 * c));
+          acc.first = min(acc.first, static_cast<unsigned long long>(at));
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < CW; ++c) {
+          const uint32_t got = *reinterpret_cast<const uint32_t*>(image + at + 4 * c);
+          acc.sum += got;
+          if (got != wire_code_word(h + (4 / CW) * c, sb, F)) {
+            acc.mism += 1;
+            acc.first = min(acc.first, static_cast<unsigned long long>(at + 4 * c));
+          }
         }
       }
       if ((iv & 3u) == 0) {
-        const uint64_t sat = t * kFullTile + nb * EB + (iv >> 2);
+        const uint64_t sat = t * kFullTile + wire_tile_scale_offset(nb, F) + (iv >> 2);
         const uint32_t got = static_cast<uint8_t>(image[sat]);
         acc.sum += got;
         if (got != sb) {
@@ -397,7 +444,7 @@ __global__ __launch_bounds__(kBlock) void verify_wire_reduced_packed_kernel(cons
 // ------------------------------------------------------------------ launch ----
 
 void check_format(WireFormat f, size_t n, const char* who) {
-  P2P_CHECK(f == WireFormat::Mxfp8 || f == WireFormat::Mxfp4, std::string(who) + ": the format is mxfp8 or mxfp4 (mxfp6 images are summed to bf16 only)");
+  P2P_CHECK(wire_format_valid(f), std::string(who) + ": the format is " + kWireFormatList);
   P2P_CHECK(n % kWireBlockBytes == 0, std::string(who) + ": the payload must be a multiple of 64 bytes (blocks of 32 bf16)");
 }
 
@@ -407,26 +454,31 @@ uint32_t last_blocks_of(size_t n) {
   return static_cast<uint32_t>(rest ? rest / kWireBlockBytes : kWireTileBlocks);
 }
 
-template <WireFormat F, bool SPLIT, bool OWN, int K = kMaxWireReduceSrcs>
+template <WireFormat F, bool SPLIT, bool OWN, bool BOTH, int K = kMaxWireReduceSrcs>
 void launch_k(int nsrc, uint32_t grid, const ReducePackArgs& a, hipStream_t stream) {
   if constexpr (K < 1) {
     P2P_FATAL("wire_reduce_packed: an op needs 1..8 sources");
   } else {
     if (nsrc == K)
-      wire_reduce_pack_kernel<F, K, SPLIT, OWN><<<grid, kBlock, 0, stream>>>(a);
+      wire_reduce_pack_kernel<F, K, SPLIT, OWN, BOTH><<<grid, kBlock, 0, stream>>>(a);
     else
-      launch_k<F, SPLIT, OWN, K - 1>(nsrc, grid, a, stream);
+      launch_k<F, SPLIT, OWN, BOTH, K - 1>(nsrc, grid, a, stream);
+  }
+}
+template <WireFormat F, bool BOTH>
+void launch_o(bool split, bool own, int nsrc, uint32_t grid, const ReducePackArgs& a, hipStream_t stream) {
+  if (own) {
+    if (split) launch_k<F, true, true, BOTH>(nsrc, grid, a, stream);
+    else launch_k<F, false, true, BOTH>(nsrc, grid, a, stream);
+  } else {
+    if (split) launch_k<F, true, false, BOTH>(nsrc, grid, a, stream);
+    else launch_k<F, false, false, BOTH>(nsrc, grid, a, stream);
   }
 }
 template <WireFormat F>
-void launch_f(bool split, bool own, int nsrc, uint32_t grid, const ReducePackArgs& a, hipStream_t stream) {
-  if (own) {
-    if (split) launch_k<F, true, true>(nsrc, grid, a, stream);
-    else launch_k<F, false, true>(nsrc, grid, a, stream);
-  } else {
-    if (split) launch_k<F, true, false>(nsrc, grid, a, stream);
-    else launch_k<F, false, false>(nsrc, grid, a, stream);
-  }
+void launch_f(bool split, bool own, bool both, int nsrc, uint32_t grid, const ReducePackArgs& a, hipStream_t stream) {
+  if (both) launch_o<F, true>(split, own, nsrc, grid, a, stream);
+  else launch_o<F, false>(split, own, nsrc, grid, a, stream);
 }
 
 }  // namespace
@@ -437,12 +489,17 @@ void launch_wire_reduce_packed(const WireReduceOp& op, WireFormat fmt, hipStream
   P2P_CHECK(!op.own_bf16 || !(op.coherent_mask & 1u), "wire_reduce_packed: a bf16 own shard (source 0) is local memory, not a peer's buffer");
   if (!op.payload_bytes) return;
   P2P_CHECK(op.dst && reinterpret_cast<uintptr_t>(op.dst) % 16 == 0, "wire_reduce_packed: 16-byte aligned buffers required");
-  ReducePackArgs a{};
-  for (int k = 0; k < op.nsrc; ++k) {
+  P2P_CHECK(reinterpret_cast<uintptr_t>(op.dst_bf16) % 16 == 0, "wire_reduce_packed: 16-byte aligned buffers required");
+  for (int k = 0; k < op.nsrc; ++k)
     P2P_CHECK(op.src[k] && reinterpret_cast<uintptr_t>(op.src[k]) % 16 == 0, "wire_reduce_packed: 16-byte aligned buffers required");
-    a.src[k] = static_cast<const char*>(op.src[k]);
+  if (fmt == WireFormat::Mxfp6) {  // a lane per block, no barrier: wire_reduce_pack6.hip
+    launch_wire_reduce_packed6(op, stream, max_blocks, lanes);
+    return;
   }
+  ReducePackArgs a{};
+  for (int k = 0; k < op.nsrc; ++k) a.src[k] = static_cast<const char*>(op.src[k]);
   a.dst = static_cast<char*>(op.dst);
+  a.dst_bf16 = static_cast<char*>(op.dst_bf16);
   a.ntiles = tiles_of(op.payload_bytes);
   a.last_blocks = last_blocks_of(op.payload_bytes);
   a.coherent = op.coherent_mask;
@@ -450,9 +507,12 @@ void launch_wire_reduce_packed(const WireReduceOp& op, WireFormat fmt, hipStream
   const uint32_t grid = static_cast<uint32_t>(std::min(a.ntiles, cap));
   // Auto: contiguous was measured faster in every cell, by 1-8% against a spread under 1% (docs/DESIGN.md): unlike
   // wire_reduce.hip, where split's two coalesced 16 B stores win.
-  const bool split = lanes == WireLanes::Auto ? false : lanes == WireLanes::Split;
-  if (fmt == WireFormat::Mxfp8) launch_f<WireFormat::Mxfp8>(split, op.own_bf16, op.nsrc, grid, a, stream);
-  else launch_f<WireFormat::Mxfp4>(split, op.own_bf16, op.nsrc, grid, a, stream);
+  // With both outputs the 8 KiB of bf16 a tile stores dominate, and split (both 16 B stores coalesced) was measured
+  // 5-86% faster in every cell against a spread under 4.4% (docs/DESIGN.md): Auto follows the output.
+  const bool both = op.dst_bf16 != nullptr;
+  const bool split = lanes == WireLanes::Auto ? both : lanes == WireLanes::Split;
+  if (fmt == WireFormat::Mxfp8) launch_f<WireFormat::Mxfp8>(split, op.own_bf16, both, op.nsrc, grid, a, stream);
+  else launch_f<WireFormat::Mxfp4>(split, op.own_bf16, both, op.nsrc, grid, a, stream);
   HIPCHECK(hipGetLastError());
 }
 
@@ -472,6 +532,8 @@ void launch_verify_wire_reduced_packed(const void* image, size_t payload_bytes, 
     const auto* p = static_cast<const char*>(image);
     if (fmt == WireFormat::Mxfp8)
       verify_wire_reduced_packed_kernel<WireFormat::Mxfp8><<<grid, kBlock, 0, stream>>>(p, nvec, tiles_of(payload_bytes), last_blocks_of(payload_bytes), s, acc);
+    else if (fmt == WireFormat::Mxfp6)
+      verify_wire_reduced_packed_kernel<WireFormat::Mxfp6><<<grid, kBlock, 0, stream>>>(p, nvec, tiles_of(payload_bytes), last_blocks_of(payload_bytes), s, acc);
     else
       verify_wire_reduced_packed_kernel<WireFormat::Mxfp4><<<grid, kBlock, 0, stream>>>(p, nvec, tiles_of(payload_bytes), last_blocks_of(payload_bytes), s, acc);
     HIPCHECK(hipGetLastError());

@@ -404,18 +404,23 @@ def reference_wire_reduce(operands, fmt: str, own_bf16: bool = False) -> torch.T
 
 
 def wire_reduce_packed_(dst: torch.Tensor, srcs, nbytes: int, fmt: str, *, coherent=False, max_blocks: int = 0,
-                        lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None, own_bf16: bool = False) -> torch.Tensor:
+                        lanes: str = "auto", stream: Optional[torch.cuda.Stream] = None, own_bf16: bool = False,
+                        both: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``dst`` = the wire image (``wire_bytes(nbytes, fmt)`` bytes) of the bf16
-    sum :func:`wire_reduce_` gives for the 1..8 wire images ``srcs`` of
-    ``nbytes`` of payload each, with the gfx950 wire-reduce-pack kernel in one
-    launch (the IPC pull engine's receive under ``--reduce-out wire``).
-    ``coherent`` and ``own_bf16`` as in :func:`wire_reduce_`."""
+    sum :func:`wire_reduce_` gives for the 1..8 'mxfp8' / 'mxfp6' / 'mxfp4' wire
+    images ``srcs`` of ``nbytes`` of payload each, with the gfx950
+    wire-reduce-pack kernel in one launch (the IPC pull engine's receive under
+    ``--reduce-out wire``).  ``coherent`` and ``own_bf16`` as in
+    :func:`wire_reduce_`.  ``both``: ``nbytes`` of bf16 that receive, in the same
+    launch, what that image widens to (``--reduce-out both``)."""
     nat = require_native()
     image = nat.wire_bytes(nbytes, fmt)
     if _check_tensor(dst) < image or any(_check_tensor(s) < (nbytes if own_bf16 and k == 0 else image) for k, s in enumerate(srcs)):
         raise ValueError("wire_reduce_packed_: dst or a source holds less than wire_bytes() of the payload")
+    if both is not None and _check_tensor(both) < nbytes:
+        raise ValueError("wire_reduce_packed_: both holds less than the payload")
     nat.wire_reduce_packed(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, fmt, _stream(stream), coherent, max_blocks, lanes,
-                           own_bf16)
+                           own_bf16, both.data_ptr() if both is not None else 0)
     return dst
 
 
