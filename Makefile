@@ -26,7 +26,7 @@ HIPFLAGS  := $(CXXSTD) $(OPT) $(WARN) -fPIC --offload-arch=$(ARCH) -Icsrc
 HOSTFLAGS := $(CXXSTD) $(OPT) $(WARN) -fPIC -Icsrc -pthread
 
 CORE      := common units stats schedule routing bootstrap transport_host transport_shm runner step_driver report provenance app rccl_log diagnose
-GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o reduce.o wire.o wire_reduce.o wire_reduce_pack.o wire_reduce_pack6.o diagnose_hip.o pingpong.o stream.o load_hip.o)
+GPU_OBJS  := $(addprefix $(BUILD)/gpu/,$(addsuffix .o,$(CORE) transport_rccl transport_ipc topology stream_gate device_checks load hip_stream) kernels.o reduce.o reduce_gate.o wire.o wire_reduce.o wire_reduce_pack.o wire_reduce_pack6.o diagnose_hip.o pingpong.o stream.o load_hip.o)
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(addsuffix .o,$(CORE) transport_rccl_stub))
 
 # MPICH lives in /opt/conda; putting /opt/conda/lib on the rpath would pull in
@@ -103,6 +103,11 @@ $(BUILD)/gpu/kernels.o: csrc/kernels.hip $(HEADERS) | $(BUILD)/gpu
 # packed f32 instructions in this object.
 $(BUILD)/gpu/reduce.o: csrc/reduce.hip $(HEADERS) | $(BUILD)/gpu
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
+# The gated sum multiplies bf16 by bf16 gates: exact products, so fused and
+# packed forms give the same bits and the default flags stand.
+$(BUILD)/gpu/reduce_gate.o: csrc/reduce_gate.hip $(HEADERS) | $(BUILD)/gpu
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The wire-format kernels convert with the scaled conversion instructions and
 # integer arithmetic only: no packed f32 instructions in this object either.

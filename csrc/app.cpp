@@ -172,6 +172,16 @@ data
                          follow, one rounding.  Peers still pull this rank's image.  Works
                          with --reduce-out wire (mxfp8, mxfp4) and both.  Same transports and
                          exclusions as --reduce-wire
+      --reduce-gate H    with --reduce bf16: the receiver's one launch is a gated sum over rows
+                         of H bf16 elements, the combine of an expert-parallel MoE layer:
+                         y[r] = sum_k g[r][k] * x_k[r], operand 0 the own shard, then the
+                         incoming messages.  The gates (topk_weights, 8 bf16 = 16 B per row,
+                         positive, in [2^-4, 1)) live on the receiver; the gfx950 gated reduce
+                         kernel reads a row's entry once per wave through the scalar cache
+                         and multiplies as it sums in f32, one rounding.  H is a multiple of
+                         512 and every size a multiple of 2H bytes; at most 8 operands per
+                         rank (ring: 2; allpairs: up to 8 ranks).  Not with --reduce-wire;
+                         otherwise same transports and exclusions as --reduce
       --diagnose N       after a failed check, each rank says where its first N wrong
                          (generation, slot) deliveries differ and what they hold instead:
                          poison, a stale generation, another sender's or a misplaced
@@ -323,7 +333,7 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                                     "--warmup", "--timing", "--latency-size", "--latency-iters", "--latency-preposted", "--verify-impl",
                                     "--transport", "--ipc-engine", "--bootstrap", "--device", "--timeout", "--min-gbs", "--json",
                                     "--csv", "--trace", "--cells", "--comms", "--fuzz", "--repeat", "--diagnose", "--load", "--stream-sizes",
-                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire", "--reduce-wire", "--reduce-out", "--reduce-own"};
+                                    "--stream-depth", "--stream-channels", "--stream-iters", "--reduce", "--wire", "--reduce-wire", "--reduce-out", "--reduce-own", "--reduce-gate"};
     for (const char* v : kValued)
       if (a == v && !has_eq && i + 1 >= argc) {
         missing = true;
@@ -458,6 +468,8 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
         return false;
       }
       cfg->run.reduce_own = v == "bf16" ? ReduceOwn::Bf16 : ReduceOwn::Wire;
+    } else if (a == "--reduce-gate") {
+      cfg->run.reduce_gate = static_cast<size_t>(int_arg(1));
     } else if (a == "--load") {
       const std::string v = next();
       std::string why;
@@ -636,6 +648,38 @@ bool parse_cli(int argc, char** argv, AppConfig* cfg, int* exit_code, FILE* out)
                          "that sum of wire images is (the receiver's unquantised shard)\n");
     *exit_code = 1;
     return false;
+  }
+  // --reduce-gate: --reduce bf16 as a gated sum over rows, so it needs that
+  // option and whole rows; what --reduce refuses is refused here first, under
+  // this option's name.
+  if (cfg->run.reduce_gate) {
+    const size_t h = cfg->run.reduce_gate;
+    std::string why;
+    if (cfg->run.reduce != ReduceType::Bf16)
+      why = "needs --reduce bf16: it makes that sum a gated sum over rows of bf16";
+    if (why.empty() && cfg->run.reduce_wire != WireFormat::Off)
+      why = "cannot be combined with --reduce-wire: the gated sum reads bf16 operands (gated sums of wire images are not built)";
+    if (why.empty() && h % kGateRowMultiple)
+      why = strfmt("%zu: the row length is a multiple of 512 elements (a row is whole KiB, so a wave's 1 KiB lies in one row)", h);
+    if (why.empty() && !(cfg->transport == "host" || (cfg->transport == "ipc" && cfg->ipc_engine == "kernel")))
+      why = strfmt("needs --transport ipc --ipc-engine kernel (the gfx950 gated reduce kernel) or --transport host; %s%s%s sums nothing",
+                   cfg->transport.c_str(), cfg->transport == "ipc" ? " --ipc-engine " : "",
+                   cfg->transport == "ipc" ? cfg->ipc_engine.c_str() : "");
+    for (size_t b : cfg->sizes)
+      if (why.empty() && b % (2 * h)) why = strfmt("%zu sums whole rows: size %zu is not a multiple of %zu bytes", h, b, 2 * h);
+    if (why.empty() && cfg->run.inline_check)
+      why = "cannot be combined with --verify-inline: that check compares a copied message with one sender's stream";
+    if (why.empty() && cfg->run.diagnose > 0)
+      why = "cannot be combined with --diagnose: the diagnosis explains a slot by one sender's streams";
+    if (why.empty() && cfg->reference_buffers)  // set by --reference alone
+      why = "cannot be combined with --reference: that is the reference's run, which only moves its payload";
+    if (why.empty() && cfg->resume)
+      why = "cannot be combined with --resume: the runs in the file are counted by mode, direction and size alone";
+    if (!why.empty()) {
+      std::fprintf(stderr, "p2p_matrix: --reduce-gate %s\n", why.c_str());
+      *exit_code = 1;
+      return false;
+    }
   }
   // --reduce-wire: the sum of --reduce bf16 over operands that arrive as wire
   // images; only where a data plane can do both at once (the pull engine's
@@ -1202,6 +1246,15 @@ int run_app(const AppConfig& cfg, Bootstrap& boot, FILE* out, AppResult* result)
     return 0;
   }
 
+  // --reduce-gate: a table entry holds 8 gates, one per operand of a rank's sum.
+  for (const auto& s : scheds)
+    if (cfg.run.reduce_gate && s.max_recv_slots() + 1 > kGateSlots) {
+      if (root)
+        std::fprintf(stderr, "p2p_matrix: --reduce-gate sums at most 8 operands per rank (a gate entry holds 8): %s gives a rank "
+                             "%d (its own shard + %d incoming)\n", s.name().c_str(), s.max_recv_slots() + 1, s.max_recv_slots());
+      return 1;
+    }
+
   Placement pl = check_placement(boot);
   if (!pl.ok) P2P_FATAL("process placement check failed: " + pl.error);
   TransportOptions topt;
@@ -1236,7 +1289,7 @@ int run_app(const AppConfig& cfg, Bootstrap& boot, FILE* out, AppResult* result)
   // --reduce-own bf16: a third arena, one own shard per generation (nothing is allocated without the option).
   const size_t send_bytes = slot_stride_bytes(max_bytes) * static_cast<size_t>(run_cfg.run.gens);
   Buffers bufs(*t, max_bytes, slots * run_cfg.run.gens, send_bytes, cfg.run.reduce_own == ReduceOwn::Bf16 ? send_bytes : 0,
-               cfg.run.reduce_out == ReduceOut::Both ? send_bytes : 0);
+               cfg.run.reduce_out == ReduceOut::Both ? send_bytes : 0, cfg.run.reduce_gate ? gate_arena_bytes(send_bytes) : 0);
 
   // Connection warm-up outside any timed cell (the reference pays lazy p2p
   // connection setup inside its first cells; --reference keeps that).

@@ -78,6 +78,17 @@ VerifyResult DeviceChecks::verify_reduced(const void* p, size_t bytes, const std
   return verify_result();
 }
 
+VerifyResult DeviceChecks::verify_gated_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds,
+                                                uint64_t gate_seed, size_t row_elems, hipStream_t stream,
+                                                const StreamWait& wait) {
+  acc_.reserve(dev::kVerifyShards, [] {});
+  dev::launch_verify_reset(acc_.device(), stream);
+  dev::launch_verify_gated_reduced(p, bytes, seeds.data(), static_cast<int>(seeds.size()), gate_seed, row_elems, acc_.device(), stream);
+  acc_.readback(1, stream);
+  wait();
+  return verify_result();
+}
+
 VerifyResult DeviceChecks::verify_unpacked(const void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt,
                                            hipStream_t stream, const StreamWait& wait) {
   acc_.reserve(dev::kVerifyShards, [] {});

@@ -80,6 +80,9 @@ class DeviceChecks {
   // Blocking: reset + the reduced check + finalize + readback.
   VerifyResult verify_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, ReduceType dtype,
                               hipStream_t stream, const StreamWait& wait);
+  // The same for a gated sum (Transport::verify_reduced_gated; kernels.hpp launch_verify_gated_reduced).
+  VerifyResult verify_gated_reduced(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, uint64_t gate_seed,
+                                    size_t row_elems, hipStream_t stream, const StreamWait& wait);
 
   // ---- unpacked buffer (Transport::verify_unpacked; kernels.hpp launch_verify_unpacked) ----
   // Blocking: reset + the unpacked check + finalize + readback.

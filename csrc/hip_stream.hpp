@@ -81,6 +81,16 @@ class GpuTransport : public Transport {
     return checks_.verify_reduced(p, bytes, seeds, dtype, stream_, [this] { sync(); });
   }
 
+  void fill_gate(void* p, size_t rows, uint64_t seed) override {
+    before_buffer_work();
+    dev::launch_fill_gate(p, rows, seed, stream_);
+  }
+  VerifyResult verify_reduced_gated(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, uint64_t gate_seed,
+                                    size_t row_elems) override {
+    before_buffer_work();
+    return checks_.verify_gated_reduced(p, bytes, seeds, gate_seed, row_elems, stream_, [this] { sync(); });
+  }
+
   void fill_packed(void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt) override {
     before_buffer_work();
     dev::launch_fill_packed(p, payload_bytes, seed, fmt, stream_);

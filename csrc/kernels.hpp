@@ -27,6 +27,9 @@
 //   sum     — multi-source receive-and-reduce for the IPC transport (--reduce,
 //             reduce.hip): K loads in flight per lane, one store; with it the
 //             operand fill and the check of a reduced buffer
+//   gsum    — the same launch as a gated sum over rows (--reduce-gate,
+//             reduce_gate.hip): the expert combine, a row's 8 gates read once
+//             per wave through the scalar cache; the gate fill and the check
 //   wire    — block-scaled payloads for the IPC transport (--wire, wire.hip):
 //             the receive that widens MXFP8 / MXFP4 to bf16 as it pulls, the
 //             sender's pack, and the check of an unpacked buffer
@@ -50,6 +53,7 @@
 #include <cstdint>
 
 #include "prng.hpp"
+#include "reduce_gate_op.hpp"
 #include "reduce_op.hpp"
 #include "wire_op.hpp"
 #include "wire_reduce_op.hpp"
@@ -214,6 +218,36 @@ void launch_fill_operand(void* p, size_t bytes, uint64_t seed, ReduceType dtype,
 // launch_verify's (reset acc first).  Register staging: never inside timing.
 void launch_verify_reduced(const void* p, size_t bytes, const uint64_t* seeds, int nseeds, ReduceType dtype,
                            VerifyAccum* acc, hipStream_t stream);
+
+// ---- gated receive-and-reduce (reduce_gate.hip; --reduce-gate) ----
+// The expert combine of a MoE layer in the same one launch: op i's `bytes` are
+// rows of row_elems bf16 (a multiple of 512, so a row is whole KiB; bytes whole
+// rows: P2P_CHECKs), and row r of dst is sum_k gate[r][k] * src[k][r]
+// (reduce_gate_op.hpp: f32 chains in operand order, one rounding).  `gate` is
+// local memory, bytes / (2 * row_elems) entries of 16 B (8 bf16 gates, gate k
+// operand k's), read-only while the kernel runs.  A wave's 1 KiB lies in one
+// row: it reads that row's entry once per chunk with a scalar 16 B load issued
+// ahead of the lane's nsrc vector loads, and the gates enter the multiplies as
+// scalar operands.  Sources, dst, coherent_mask, max_blocks and the grouping of
+// ops into launches (equal nsrc, up to kMaxReduceOps) as launch_multi_reduce;
+// ops above 4 GiB go in pieces of whole rows.  No tail path.
+struct GatedReduceOp {
+  void* dst = nullptr;
+  size_t bytes = 0;
+  int nsrc = 0;
+  const void* src[kMaxReduceSrcs] = {};
+  uint32_t coherent_mask = 0;
+  const void* gate = nullptr;
+  size_t row_elems = 0;
+};
+void launch_gated_reduce(const GatedReduceOp* ops, int nops, hipStream_t stream, int max_blocks = 0);
+// `rows` table entries from PRNG stream `seed` (reduce_gate_op.hpp gate_word): gates in [2^-4, 1).
+void launch_fill_gate(void* p, size_t rows, uint64_t seed, hipStream_t stream);
+// launch_verify_reduced for a gated sum: regenerates the nseeds (<= 8) bf16
+// operand streams and the table of gate_seed, and compares word by word; the
+// totals end in acc[0] (reset acc first).  Never inside timing.
+void launch_verify_gated_reduced(const void* p, size_t bytes, const uint64_t* seeds, int nseeds, uint64_t gate_seed,
+                                 size_t row_elems, VerifyAccum* acc, hipStream_t stream);
 
 // ---- block-scaled wire formats (wire.hip; --wire) ----
 // The pull engine's third data plane: op i reads the MXFP8 / MXFP4 wire image

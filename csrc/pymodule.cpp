@@ -114,7 +114,7 @@ class Session {
                   const std::string& timing, bool verify, bool warm, const std::vector<std::pair<int, int>>& cells,
                   int diagnose, bool inline_check, const std::string& load, const std::string& reduce,
                   const std::string& wire, const std::string& reduce_wire, const std::string& reduce_out,
-                  const std::string& reduce_own) {
+                  const std::string& reduce_own, size_t reduce_gate) {
     LoadSpec load_spec;
     std::string why;
     P2P_CHECK(load.empty() || parse_load_spec(load, &load_spec, &why), "load '" + load + "': " + why);
@@ -169,6 +169,12 @@ class Session {
               "reduce_own='bf16' needs reduce='bf16' and reduce_wire (it says what operand 0 of that sum of wire images is)");
     const bool own_shard = reduce_own == "bf16";
     if (own_shard) cfg.reduce_own = ReduceOwn::Bf16;
+    // reduce_gate=H: the sum is gated over rows of H bf16 (RunConfig::reduce_gate).
+    P2P_CHECK(!reduce_gate || (cfg.reduce == ReduceType::Bf16 && cfg.reduce_wire == WireFormat::Off && t_->supports_reduce_gate() &&
+                               gate_rows(bytes, reduce_gate) > 0 && s.max_recv_slots() < kGateSlots),
+              "reduce_gate needs reduce='bf16' without reduce_wire, transport 'ipc' / 'ipc:kernel' or 'host', a row length that is a "
+              "multiple of 512, bytes a multiple of 2 * reduce_gate and at most 8 operands per rank");
+    cfg.reduce_gate = reduce_gate;
     const int slots = std::max(1, s.max_recv_slots());
     // Verified runs: one receive generation per iteration, as far as memory
     // allows (runner.hpp RunConfig::gens).
@@ -176,7 +182,8 @@ class Session {
     cfg.gens = verify ? verify_generations(*t_, *boot_, bytes, slots, std::max(iters, warmup), own_shard + both) : 1;
     if (const char* rc = std::getenv("P2P_RECHUNK")) cfg.rechunk = std::atoi(rc) != 0;
     const size_t send_bytes = slot_stride_bytes(bytes) * static_cast<size_t>(cfg.gens);
-    Buffers bufs(*t_, bytes, slots * cfg.gens, send_bytes, own_shard ? send_bytes : 0, both ? send_bytes : 0);
+    Buffers bufs(*t_, bytes, slots * cfg.gens, send_bytes, own_shard ? send_bytes : 0, both ? send_bytes : 0,
+                 reduce_gate ? gate_arena_bytes(send_bytes) : 0);
     if (warm) {
       warm_connections(*t_, *boot_, s, bufs);
       t_->refine_op_limits(*boot_);
@@ -478,6 +485,51 @@ py::tuple device_verify_reduced(uintptr_t ptr, size_t bytes, const std::vector<u
   {
     py::gil_scoped_release nogil;
     r = c.verify_reduced(reinterpret_cast<const void*>(ptr), bytes, seeds, t, st, stream_wait(st));
+  }
+  return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
+}
+
+// ---- gated receive-and-reduce (kernels.hpp GatedReduceOp) on raw pointers ----
+dev::GatedReduceOp gated_op_arg(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t bytes, uintptr_t gate, size_t row_elems,
+                                bool coherent) {
+  if (srcs.empty() || srcs.size() > static_cast<size_t>(dev::kMaxReduceSrcs)) throw py::value_error("gated_reduce: 1..8 sources");
+  if (!gate_rows(bytes, row_elems))
+    throw py::value_error("gated_reduce: row_elems is a multiple of 512 and bytes a non-zero multiple of 2 * row_elems");
+  dev::GatedReduceOp op;
+  op.dst = reinterpret_cast<void*>(dst);
+  op.bytes = bytes;
+  op.gate = reinterpret_cast<const void*>(gate);
+  op.row_elems = row_elems;
+  for (uintptr_t s : srcs) op.src[op.nsrc++] = reinterpret_cast<const void*>(s);
+  if (coherent) op.coherent_mask = dev::kReduceDstCoherent | ((1u << op.nsrc) - 1u);  // the table stays a local read
+  return op;
+}
+
+void device_gated_reduce(uintptr_t dst, const std::vector<uintptr_t>& srcs, size_t bytes, uintptr_t gate, size_t row_elems,
+                         uintptr_t stream, bool coherent, int max_blocks) {
+  const dev::GatedReduceOp op = gated_op_arg(dst, srcs, bytes, gate, row_elems, coherent);
+  dev::launch_gated_reduce(&op, 1, as_stream(stream), max_blocks);
+}
+
+// One launch_gated_reduce over [(dst, [srcs], bytes, gate)], 1..8 sources each.
+void device_gated_reduce_many(const std::vector<std::tuple<uintptr_t, std::vector<uintptr_t>, size_t, uintptr_t>>& ops,
+                              size_t row_elems, uintptr_t stream, bool coherent, int max_blocks) {
+  std::vector<dev::GatedReduceOp> v;
+  for (const auto& o : ops) v.push_back(gated_op_arg(std::get<0>(o), std::get<1>(o), std::get<2>(o), std::get<3>(o), row_elems, coherent));
+  dev::launch_gated_reduce(v.data(), static_cast<int>(v.size()), as_stream(stream), max_blocks);
+}
+
+py::tuple device_verify_gated_reduced(uintptr_t ptr, size_t bytes, const std::vector<uint64_t>& seeds, uint64_t gate_seed,
+                                      size_t row_elems, uintptr_t stream) {
+  if (seeds.empty() || seeds.size() > static_cast<size_t>(dev::kMaxReduceSrcs)) throw py::value_error("verify_gated_reduced: 1..8 seeds");
+  if (!gate_rows(bytes, row_elems))
+    throw py::value_error("verify_gated_reduced: row_elems is a multiple of 512 and bytes a non-zero multiple of 2 * row_elems");
+  DeviceChecks& c = checks_for_current_device();
+  hipStream_t st = as_stream(stream);
+  VerifyResult r;
+  {
+    py::gil_scoped_release nogil;
+    r = c.verify_gated_reduced(reinterpret_cast<const void*>(ptr), bytes, seeds, gate_seed, row_elems, st, stream_wait(st));
   }
   return py::make_tuple(r.mismatches, r.checksum, r.first_bad);
 }
@@ -1091,7 +1143,7 @@ PYBIND11_MODULE(_p2pcore, m) {
            py::arg("iters") = 128, py::arg("warmup") = 8, py::arg("timing") = "events", py::arg("verify") = false,
            py::arg("warm") = true, py::arg("cells") = std::vector<std::pair<int, int>>{}, py::arg("diagnose") = 0,
            py::arg("inline_check") = false, py::arg("load") = "", py::arg("reduce") = "", py::arg("wire") = "",
-           py::arg("reduce_wire") = "", py::arg("reduce_out") = "", py::arg("reduce_own") = "", py::call_guard<NativeCall, py::gil_scoped_release>())
+           py::arg("reduce_wire") = "", py::arg("reduce_out") = "", py::arg("reduce_own") = "", py::arg("reduce_gate") = 0, py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("gate_probe", &Session::gate_probe, py::arg("timeout_s") = 0.2, py::arg("release") = true,
            py::call_guard<NativeCall, py::gil_scoped_release>())
       .def("device_latency", &Session::device_latency, py::arg("bytes") = 8, py::arg("iters") = 1000,
@@ -1308,6 +1360,40 @@ PYBIND11_MODULE(_p2pcore, m) {
         return py::bytes(out);
       }, py::arg("operands"), py::arg("dtype"),
       "CPU sum of equal-sized operand byte strings in order, bit-compatible with the reduce kernel.");
+  m.def("gated_reduce", &device_gated_reduce, py::arg("dst"), py::arg("srcs"), py::arg("bytes"), py::arg("gate"),
+        py::arg("row_elems"), py::arg("stream") = 0, py::arg("coherent") = false, py::arg("max_blocks") = 0,
+        "The IPC transport's gfx950 gated reduce kernel (the expert combine): rows of row_elems bf16 (a multiple of 512), row r of "
+        "dst = sum_k gate[r][k] * srcs[k][r] in f32 in that order, rounded once; gate: bytes / (2 * row_elems) local entries of 8 "
+        "bf16 (coherent: every source and dst in the cross-GPU form).");
+  m.def("gated_reduce_many", &device_gated_reduce_many, py::arg("ops"), py::arg("row_elems"), py::arg("stream") = 0,
+        py::arg("coherent") = false, py::arg("max_blocks") = 0,
+        "The gated reduce kernel over several (dst, [srcs], bytes, gate) ops, 1..8 sources each; consecutive ops of equal "
+        "fan-in share a launch.");
+  m.def("fill_gate", [](uintptr_t ptr, size_t rows, uint64_t seed, uintptr_t stream) {
+        dev::launch_fill_gate(reinterpret_cast<void*>(ptr), rows, seed, as_stream(stream));
+      }, py::arg("ptr"), py::arg("rows"), py::arg("seed"), py::arg("stream") = 0,
+      "Fills `rows` gate table entries (16 B, 8 bf16 gates in [2**-4, 1)) from stream `seed` (csrc/reduce_gate_op.hpp).");
+  m.def("verify_gated_reduced", &device_verify_gated_reduced, py::arg("ptr"), py::arg("bytes"), py::arg("seeds"),
+        py::arg("gate_seed"), py::arg("row_elems"), py::arg("stream") = 0,
+        "Compares the buffer with the gated sum of the bf16 operand streams `seeds` under the gate table of `gate_seed`: "
+        "(wrong 32-bit words, checksum, first bad byte offset or 2**64-1).");
+  m.def("host_gated_reduce", [](const std::vector<py::bytes>& operands, const py::bytes& gate, size_t row_elems) {
+        if (operands.empty() || operands.size() > static_cast<size_t>(kGateSlots)) throw py::value_error("host_gated_reduce: 1..8 operands");
+        std::vector<std::string> data(operands.begin(), operands.end());
+        const std::string table = gate;
+        const size_t rows = gate_rows(data[0].size(), row_elems);
+        if (!rows || table.size() != rows * kGateEntryBytes)
+          throw py::value_error("host_gated_reduce: whole rows of row_elems (a multiple of 512) bf16 and 16 bytes of gates per row");
+        std::vector<const void*> p;
+        for (const std::string& d : data) {
+          if (d.size() != data[0].size()) throw py::value_error("host_gated_reduce: equal sizes");
+          p.push_back(d.data());
+        }
+        std::string out(data[0].size(), '\0');
+        host_gated_reduce(&out[0], p.data(), static_cast<int>(p.size()), out.size(), table.data(), row_elems);
+        return py::bytes(out);
+      }, py::arg("operands"), py::arg("gate"), py::arg("row_elems"),
+      "CPU gated sum of equal-sized operand byte strings in order, bit-compatible with the gated reduce kernel.");
   m.def("wire_bytes", [](size_t payload_bytes, const std::string& fmt) {
         return wire_bytes(wire_payload_arg(payload_bytes), wire_format_arg(fmt));
       }, py::arg("payload_bytes"), py::arg("fmt"), "Size of the wire image of payload_bytes of bf16 (csrc/wire_op.hpp).");

@@ -232,6 +232,7 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
   if (rec.cfg.reduce_out == ReduceOut::Wire) head.insert(head.size() - 1, " reduce-out=wire");
   if (rec.cfg.reduce_out == ReduceOut::Both) head.insert(head.size() - 1, " reduce-out=both");
   if (rec.cfg.reduce_own == ReduceOwn::Bf16) head.insert(head.size() - 1, " reduce-own=bf16");
+  if (rec.cfg.reduce_gate) head.insert(head.size() - 1, strfmt(" reduce-gate=%zu", rec.cfg.reduce_gate));
   std::fprintf(out, "\n== %s ==\n", head.c_str());
   bool blank_diag = rec.mode != Mode::Self && n > 1;
   auto gbs = flow_matrix_gbs(rec, n);
@@ -282,6 +283,9 @@ void print_extended(FILE* out, const RunRecord& rec, int n) {
   else if (rec.cfg.reduce != ReduceType::Off)
     std::fprintf(out, "  reduce: %s, every receiver sums its own shard and its incoming messages in one launch\n",
                  reduce_type_name(rec.cfg.reduce));
+  if (rec.cfg.reduce_gate)
+    std::fprintf(out, "  reduce-gate: the sum is gated, rows of %zu bf16: row r = sum_k gate[r][k] * operand k's row r (%llu rows, 16 B of gates each)\n",
+                 rec.cfg.reduce_gate, static_cast<unsigned long long>(gate_rows(rec.cfg.bytes, rec.cfg.reduce_gate)));
   if (rec.cfg.reduce_own == ReduceOwn::Bf16)
     std::fprintf(out, "  reduce-own: operand 0 is the receiver's own shard in bf16 (%llu bytes, never quantised), not its image\n",
                  static_cast<unsigned long long>(rec.cfg.bytes));
@@ -436,6 +440,7 @@ std::string run_to_json(const RunRecord& rec, int n) {
         << "\",\"bytes\":" << wire_bytes(rec.cfg.bytes, rec.cfg.reduce_wire)
         << (rec.cfg.reduce_out == ReduceOut::Both ? ",\"both\":true}" : "}");
     if (rec.cfg.reduce_own == ReduceOwn::Bf16) o << ",\"own\":\"bf16\"";  // --reduce-own bf16: operand 0 is unquantised
+    if (rec.cfg.reduce_gate) o << ",\"gate\":{\"row_elems\":" << rec.cfg.reduce_gate << "}";  // --reduce-gate H: a gated sum
     o << "}";
   }
   if (rec.cfg.wire != WireFormat::Off)  // present only when the option is on

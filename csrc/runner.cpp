@@ -35,14 +35,15 @@ namespace detail {
 size_t slot_stride(size_t bytes) { return (std::max<size_t>(bytes, 16) + 4095) / 4096 * 4096; }
 }  // namespace detail
 
-Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes, size_t own_bytes, size_t image_bytes)
+Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes, size_t own_bytes, size_t image_bytes,
+                 size_t gate_bytes)
     : t_(t), cap_(std::max<size_t>(slot_bytes, 16)), send_cap_(std::max(send_bytes, cap_)), stride_(slot_stride(cap_)),
-      nslots_(std::max(recv_slots, 1)), own_cap_(own_bytes), image_cap_(image_bytes) {
+      nslots_(std::max(recv_slots, 1)), own_cap_(own_bytes), image_cap_(image_bytes), gate_cap_(gate_bytes) {
   // One send buffer + one receive arena: check against free HBM up front so a
   // 288 GB sweep fails with an explanation instead of a hipMalloc error mid-run.
   size_t free_b = 0, total_b = 0;
   const double arena = static_cast<double>(stride_) * static_cast<double>(nslots_);
-  const double need = static_cast<double>(send_cap_) + arena + static_cast<double>(own_cap_) + static_cast<double>(image_cap_);
+  const double need = static_cast<double>(send_cap_) + arena + static_cast<double>(own_cap_) + static_cast<double>(image_cap_) + static_cast<double>(gate_cap_);
   if (t_.mem_info(&free_b, &total_b) && need > 0.98 * static_cast<double>(free_b))
     P2P_FATAL(strfmt("buffers need %.2f GiB (send %s + %d receive slots of %s) but only %.2f of %.2f GiB are free on "
                      "this GPU; use a smaller --size/--sizes maximum or a mode with fewer concurrent peers",
@@ -52,6 +53,7 @@ Buffers::Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_by
   recv_ = t_.alloc(stride_ * static_cast<size_t>(nslots_));
   if (own_cap_) own_ = t_.alloc(own_cap_);  // local operands only: not part of the registered set
   if (image_cap_) image_ = t_.alloc(image_cap_);  // local outputs only: not registered either
+  if (gate_cap_) gate_ = t_.alloc(gate_cap_);  // the gate tables: local operands of this rank's sums only
   Transport::BufferSet set;
   set.send = send_;
   set.send_bytes = send_cap_;
@@ -68,6 +70,7 @@ Buffers::~Buffers() {
   // on, so the first error is the one that surfaces.
   try {
     t_.unregister_buffers(send_);
+    if (gate_) t_.release(gate_);
     if (image_) t_.release(image_);
     if (own_) t_.release(own_);
     if (recv_) t_.release(recv_);
@@ -141,7 +144,7 @@ std::vector<Transport::GroupFlow> group_flow_list(const Phase& phase) {
 
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen,
                           const InlineRecords* check, ReduceType reduce, WireFormat wire, WireFormat reduce_wire,
-                          ReduceOut reduce_out, ReduceOwn reduce_own) {
+                          ReduceOut reduce_out, ReduceOwn reduce_own, size_t reduce_gate) {
   const RankOps& ops = phase.ranks[static_cast<size_t>(t.rank())];
   const std::vector<int> rs = remote_slots(phase, t.rank());
   const int base = gen * std::max(1, phase.max_recv_slots());
@@ -171,7 +174,13 @@ void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffer
     t.reduce_packed_from(bufs.recv_buf(base), bytes, own, ops.recv_from, off, reduce_wire, own_bf16);
   else if (reduce_wire != WireFormat::Off && !ops.recv_from.empty())
     t.reduce_unpacked_from(bufs.recv_buf(base), bytes, own, ops.recv_from, off, reduce_wire, own_bf16);
-  else if (reduce != ReduceType::Off && !ops.recv_from.empty())
+  else if (reduce_gate && reduce != ReduceType::Off && !ops.recv_from.empty()) {
+    // The generation's gate table: gate_rows(bytes) entries at the scaled send offset.
+    P2P_CHECK(gate_arena_bytes(off) + gate_rows(bytes, reduce_gate) * kGateEntryBytes <= bufs.gate_capacity(),
+              "reduce_gate: the buffers hold no gate table for this generation");
+    t.reduce_gated_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, bufs.gate_at(gate_arena_bytes(off)),
+                        reduce_gate);
+  } else if (reduce != ReduceType::Off && !ops.recv_from.empty())
     t.reduce_from(bufs.recv_buf(base), bytes, bufs.send_at(off), ops.recv_from, off, reduce);
   for (size_t i = 0; reduce == ReduceType::Off && i < ops.recv_from.size(); ++i) {
     if (wire != WireFormat::Off)
@@ -189,6 +198,10 @@ size_t slot_stride_bytes(size_t bytes) { return slot_stride(bytes); }
 
 uint64_t generation_seed(int src, size_t bytes, uint64_t salt, int gen) {
   return payload_seed(src, bytes, gen == 0 ? salt : salt ^ (static_cast<uint64_t>(gen) << 40));
+}
+
+uint64_t gate_generation_seed(int receiver, size_t bytes, uint64_t salt, int gen) {
+  return generation_seed(receiver, bytes, salt, gen) ^ 0x6A09E667F3BCC909ull;  // never an operand stream's seed
 }
 
 size_t shared_free_budget(Transport& t, Bootstrap& boot, size_t fallback, size_t cap) {
@@ -260,6 +273,13 @@ void prepare_payload(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
     for (int g = 0; g < gens && !(ops.send_to.empty() && ops.recv_from.empty()); ++g)
       t.fill_operand(bufs.send_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes,
                      generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.reduce);
+    // --reduce-gate: a receiver's gate table of every generation, in the gate arena.
+    for (int g = 0; g < gens && cfg.reduce_gate && !ops.recv_from.empty(); ++g) {
+      const size_t at = gate_arena_bytes(slot_stride(cfg.bytes) * static_cast<size_t>(g));
+      const size_t rows = gate_rows(cfg.bytes, cfg.reduce_gate);
+      P2P_CHECK(at + rows * kGateEntryBytes <= bufs.gate_capacity(), "reduce_gate: the buffers hold no gate table for this generation");
+      t.fill_gate(bufs.gate_at(at), rows, gate_generation_seed(t.rank(), cfg.bytes, cfg.salt, g));
+    }
   } else if (cfg.wire != WireFormat::Off) {
     // The region at a generation's usual offset holds the wire image of its stream.
     for (int g = 0; g < gens && !ops.send_to.empty(); ++g)
@@ -298,6 +318,9 @@ uint64_t check_slots(Transport& t, const Phase& phase, const RunConfig& cfg, Buf
                                  ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire, own_bf16, true)
                                  : cfg.reduce_wire != WireFormat::Off
                                  ? t.verify_reduced_unpacked(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce_wire, own_bf16)
+                                 : cfg.reduce_gate
+                                 ? t.verify_reduced_gated(bufs.recv_buf(g * per), cfg.bytes, seeds,
+                                                          gate_generation_seed(t.rank(), cfg.bytes, cfg.salt, g), cfg.reduce_gate)
                                  : t.verify_reduced(bufs.recv_buf(g * per), cfg.bytes, seeds, cfg.reduce);
       if (cfg.reduce_out == ReduceOut::Both)  // and the image beside it: the two outputs' mismatches add up
         v.mismatches += t.verify_reduced_packed(bufs.image_at(slot_stride(cfg.bytes) * static_cast<size_t>(g)), cfg.bytes, seeds,
@@ -477,7 +500,7 @@ void rechunk_until_warmup_verifies(Transport& t, Bootstrap& boot, const Phase& p
     }
     boot.barrier();
     if (active) {
-      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own);
+      for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own, cfg.reduce_gate);
       t.sync();
     }
     bad = boot.allreduce_sum_u64(local_mismatches());
@@ -667,6 +690,14 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   }
   P2P_CHECK(cfg.reduce_out == ReduceOut::Bf16 || cfg.reduce_wire != WireFormat::Off,
             "reduce_out wire / both: only with reduce_wire (the image's format is the operands')");
+  if (cfg.reduce_gate) {
+    P2P_CHECK(cfg.reduce == ReduceType::Bf16 && cfg.reduce_wire == WireFormat::Off,
+              "reduce_gate: only with reduce bf16 and without reduce_wire (the gated sum of bf16 rows)");
+    P2P_CHECK(t.supports_reduce_gate(), "reduce_gate: this transport has no gated sum (ipc with the kernel engine, or host)");
+    P2P_CHECK(gate_rows(cfg.bytes, cfg.reduce_gate) > 0,
+              "reduce_gate: the row length is a multiple of 512 elements and the message whole rows of it");
+    P2P_CHECK(phase.max_recv_slots() < kGateSlots, "reduce_gate: a gated sum has at most 8 operands (the own one and 7 incoming)");
+  }
   P2P_CHECK(cfg.reduce_own == ReduceOwn::Wire || cfg.reduce_wire != WireFormat::Off,
             "reduce_own bf16: only with reduce_wire (it says what operand 0 of that sum is)");
   P2P_CHECK(cfg.reduce_out != ReduceOut::Wire || cfg.reduce_wire != WireFormat::Mxfp6,
@@ -698,7 +729,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   const double hooked0 = now_seconds();
   if (cfg.before_timing) cfg.before_timing();
   if (active) {
-    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own);
+    for (int i = 0; i < cfg.warmup; ++i) post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own, cfg.reduce_gate);
     t.sync();
   }
   if (cfg.verify && cfg.warmup > 0) {
@@ -742,7 +773,7 @@ PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t 
   auto post = [&](int i) {
     if (skip_some) t.set_discard(i % 2 == 0);
     const InlineRecords rec{static_cast<size_t>(i) * nrecv, cfg.salt};
-    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own);
+    post_phase_iteration(t, phase, cfg.bytes, bufs, i % gens, inline_on && nrecv ? &rec : nullptr, cfg.reduce, cfg.wire, cfg.reduce_wire, cfg.reduce_out, cfg.reduce_own, cfg.reduce_gate);
   };
 
   double my_seconds = 0;

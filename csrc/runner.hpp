@@ -121,6 +121,17 @@ struct RunConfig {
   // seed as the image, so the checks' seeds do not change, only operand 0's
   // round trip is skipped.  Bf16 needs reduce_wire.
   ReduceOwn reduce_own = ReduceOwn::Wire;
+  // Gated sum (--reduce-gate H; transport.hpp reduce_gated_from), only with
+  // reduce = Bf16 and without reduce_wire: the row length in bf16 elements, a
+  // multiple of 512 that divides bytes / 2; 0 = off.  The one call a rank with
+  // receives posts per iteration is reduce_gated_from: the expert combine, row
+  // r of the slot = sum_k gate[r][k] * operand k's row r.  The generation's
+  // gate table lives in the gate arena of the buffers (Buffers::gate_at, local
+  // and unregistered like the own arena) and is filled before timing from
+  // gate_generation_seed(receiver, bytes, salt, gen); operands, sends, timing
+  // and reporting are `reduce`'s, the check is verify_reduced_gated.  At most 7
+  // incoming messages per rank.
+  size_t reduce_gate = 0;
   // Hooks around what a phase measures (--load brackets it with a background
   // load): run_phase calls them on every rank of a non-idle phase, in both
   // timings.  before_timing: after the payload and the poison are posted,
@@ -234,7 +245,11 @@ class Buffers {
   // memory that no peer reads: it is not registered.  image_bytes > 0 adds a
   // fourth of the same shape (RunConfig::reduce_out = Both: where a
   // generation's requantised sum goes while the receive slot takes its bf16).
-  Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes = 0, size_t own_bytes = 0, size_t image_bytes = 0);
+  // gate_bytes > 0 adds the gate arena (RunConfig::reduce_gate), local and
+  // unregistered too: gate_arena_bytes(send_bytes), generation g's table at
+  // gate_at(gate_arena_bytes(g's send offset)).
+  Buffers(Transport& t, size_t slot_bytes, int recv_slots, size_t send_bytes = 0, size_t own_bytes = 0, size_t image_bytes = 0,
+          size_t gate_bytes = 0);
   ~Buffers();
   Buffers(const Buffers&) = delete;
   Buffers& operator=(const Buffers&) = delete;
@@ -244,6 +259,8 @@ class Buffers {
   size_t own_capacity() const { return own_cap_; }
   void* image_at(size_t offset) const { return image_ ? static_cast<char*>(image_) + offset : nullptr; }
   size_t image_capacity() const { return image_cap_; }
+  void* gate_at(size_t offset) const { return gate_ ? static_cast<char*>(gate_) + offset : nullptr; }
+  size_t gate_capacity() const { return gate_cap_; }
   void* recv_buf(int slot) const;
   void* recv_base() const { return recv_; }
   size_t capacity() const { return cap_; }          // bytes per receive slot
@@ -263,7 +280,15 @@ class Buffers {
   void* own_ = nullptr;
   size_t image_cap_ = 0;
   void* image_ = nullptr;
+  size_t gate_cap_ = 0;
+  void* gate_ = nullptr;
 };
+
+// A gate table is 16 B per row and a row at least 1 KiB (512 bf16): 1 / 64 of
+// the payload at the most.  The gate arena mirrors the send buffer at that
+// scale, so a generation's table sits at its send offset / 64 (4 KiB strides:
+// 64 B aligned).  Too small to count in verify_generations' budget.
+constexpr size_t gate_arena_bytes(size_t send_bytes) { return send_bytes / 64; }
 
 // Receive slot on `peer` that holds messages from `me` in `phase` (position
 // of `me` in the peer's recv list).
@@ -288,11 +313,14 @@ struct InlineRecords {
 // With `reduce_wire` (and reduce = bf16), sends move the packed image and that
 // one call is Transport::reduce_unpacked_from, or reduce_packed_from with
 // `reduce_out` = Wire; with `reduce_own` = Bf16 its local operand is the
-// generation's region of the own arena, not the send region.
+// generation's region of the own arena, not the send region.  With
+// `reduce_gate` (row elements; reduce = bf16, no reduce_wire) the one call is
+// Transport::reduce_gated_from under the generation's table of the gate arena.
 void post_phase_iteration(Transport& t, const Phase& phase, size_t bytes, Buffers& bufs, int gen = 0,
                           const InlineRecords* check = nullptr, ReduceType reduce = ReduceType::Off,
                           WireFormat wire = WireFormat::Off, WireFormat reduce_wire = WireFormat::Off,
-                          ReduceOut reduce_out = ReduceOut::Bf16, ReduceOwn reduce_own = ReduceOwn::Wire);
+                          ReduceOut reduce_out = ReduceOut::Bf16, ReduceOwn reduce_own = ReduceOwn::Wire,
+                          size_t reduce_gate = 0);
 
 // Receive generations for verified runs of messages up to `max_bytes` with
 // `slots` receive slots per iteration and up to `iters` iterations: as many as
@@ -314,6 +342,8 @@ size_t slot_stride_bytes(size_t bytes);
 
 // PRNG stream of generation `gen` of a run's payload from `src`.
 uint64_t generation_seed(int src, size_t bytes, uint64_t salt, int gen);
+// PRNG stream of the gate table `receiver` uses in generation `gen` (RunConfig::reduce_gate).
+uint64_t gate_generation_seed(int receiver, size_t bytes, uint64_t salt, int gen);
 
 // Runs one phase on every rank (collective over `boot`).
 PhaseResult run_phase(Transport& t, Bootstrap& boot, const Phase& phase, size_t phase_index, const RunConfig& cfg,

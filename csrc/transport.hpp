@@ -27,6 +27,7 @@
 #include "background_load.hpp"
 #include "diagnose.hpp"
 #include "prng.hpp"
+#include "reduce_gate_op.hpp"
 #include "reduce_op.hpp"
 #include "wire_op.hpp"
 #include "wire_reduce_op.hpp"
@@ -133,6 +134,27 @@ class Transport {
                            size_t /*src_offset*/, ReduceType /*dtype*/) {}
   virtual VerifyResult verify_reduced(const void* /*p*/, size_t /*bytes*/, const std::vector<uint64_t>& /*seeds*/,
                                       ReduceType /*dtype*/) {
+    return {};
+  }
+
+  // ---- gated receive-and-reduce (--reduce-gate; reduce_gate_op.hpp) ----
+  // reduce_from of bf16 as an expert combine: `bytes` are rows of row_elems
+  // bf16 (a multiple of 512; bytes whole rows), and row r of dst is the sum over
+  // the operands k (local_src, then `peers` in order; at most 8) of gate k of
+  // entry r of `gate` times operand k's row r.  `gate` is local memory of this
+  // rank, bytes / (2 * row_elems) entries of 16 B, registered or not.  Same
+  // posting rules as reduce_from and instead of it; the IPC pull engine still
+  // needs one launch (the gfx950 gated reduce kernel), the host transport
+  // receives into scratch and sums on the CPU.  Operands are fill_operand's.
+  //   fill_gate             `rows` table entries from stream `seed`;
+  //   verify_reduced_gated  blocking: p against the gated sum of the operand
+  //                         streams `seeds` under the table of `gate_seed`.
+  virtual bool supports_reduce_gate() const { return false; }
+  virtual void fill_gate(void* /*p*/, size_t /*rows*/, uint64_t /*seed*/) {}
+  virtual void reduce_gated_from(void* /*dst*/, size_t /*bytes*/, const void* /*local_src*/, const std::vector<int>& /*peers*/,
+                                 size_t /*src_offset*/, const void* /*gate*/, size_t /*row_elems*/) {}
+  virtual VerifyResult verify_reduced_gated(const void* /*p*/, size_t /*bytes*/, const std::vector<uint64_t>& /*seeds*/,
+                                            uint64_t /*gate_seed*/, size_t /*row_elems*/) {
     return {};
   }
 

@@ -101,6 +101,58 @@ VerifyResult host_verify_reduced(const void* p, size_t bytes, const uint64_t* se
   return r;
 }
 
+// ---- gated sum over rows (reduce_gate_op.hpp) ----
+void host_gated_reduce(void* out, const void* const* operands, int k, size_t bytes, const void* gate, size_t row_elems) {
+  P2P_CHECK(k >= 1 && k <= kGateSlots, "host_gated_reduce: 1..8 operands");
+  P2P_CHECK(gate_rows(bytes, row_elems) > 0, "host_gated_reduce: whole rows of row_elems bf16, row_elems a multiple of 512");
+  const size_t row_bytes = 2 * row_elems;
+  uint32_t w[kGateSlots];
+  float g[kGateSlots];
+  for (size_t i = 0; i < bytes; i += 4) {
+    if (i % row_bytes == 0) {
+      uint32_t entry[4];
+      std::memcpy(entry, static_cast<const char*>(gate) + i / row_bytes * kGateEntryBytes, sizeof(entry));
+      for (int j = 0; j < k; ++j) g[j] = gate_value(entry, j);
+    }
+    for (int j = 0; j < k; ++j) std::memcpy(&w[j], static_cast<const char*>(operands[j]) + i, 4);
+    const uint32_t r = gated_reduce_word(w, g, k);
+    std::memcpy(static_cast<char*>(out) + i, &r, 4);
+  }
+}
+
+void host_fill_gate(void* p, size_t rows, uint64_t seed) {
+  for (size_t i = 0; i < 4 * rows; ++i) {
+    const uint32_t w = gate_word(prng_word(seed, i));
+    std::memcpy(static_cast<char*>(p) + 4 * i, &w, 4);
+  }
+}
+
+VerifyResult host_verify_gated_reduced(const void* p, size_t bytes, const uint64_t* seeds, int nseeds, uint64_t gate_seed,
+                                       size_t row_elems) {
+  P2P_CHECK(nseeds >= 1 && nseeds <= kGateSlots, "host_verify_gated_reduced: 1..8 operand seeds");
+  P2P_CHECK(gate_rows(bytes, row_elems) > 0, "host_verify_gated_reduced: whole rows of row_elems bf16, row_elems a multiple of 512");
+  const size_t row_words = row_elems / 2;
+  VerifyResult r;
+  uint32_t w[kGateSlots];
+  float g[kGateSlots];
+  for (size_t i = 0; i < bytes / 4; ++i) {
+    if (i % row_words == 0) {
+      uint32_t entry[4];
+      for (size_t j = 0; j < 4; ++j) entry[j] = gate_word(prng_word(gate_seed, i / row_words * 4 + j));
+      for (int j = 0; j < nseeds; ++j) g[j] = gate_value(entry, j);
+    }
+    for (int j = 0; j < nseeds; ++j) w[j] = operand_word(prng_word(seeds[j], i), ReduceType::Bf16);
+    uint32_t got;
+    std::memcpy(&got, static_cast<const char*>(p) + 4 * i, 4);
+    r.checksum += got;
+    if (got != gated_reduce_word(w, g, nseeds)) {
+      if (!r.mismatches) r.first_bad = 4 * i;
+      ++r.mismatches;
+    }
+  }
+  return r;
+}
+
 // ---- block-scaled wire formats (wire_op.hpp): tile by tile, block by block ----
 namespace {
 
@@ -426,6 +478,22 @@ class HostTransport final : public Transport {
     }
   }
 
+  // ---- gated sum: the same receives into scratch, then the CPU's gated sum ----
+  bool supports_reduce_gate() const override { return true; }
+  void fill_gate(void* p, size_t rows, uint64_t seed) override { host_fill_gate(p, rows, seed); }
+  VerifyResult verify_reduced_gated(const void* p, size_t bytes, const std::vector<uint64_t>& seeds, uint64_t gate_seed,
+                                    size_t row_elems) override {
+    return host_verify_gated_reduced(p, bytes, seeds.data(), static_cast<int>(seeds.size()), gate_seed, row_elems);
+  }
+  void reduce_gated_from(void* dst, size_t bytes, const void* local_src, const std::vector<int>& peers, size_t src_offset,
+                         const void* gate, size_t row_elems) override {
+    P2P_CHECK(peers.size() < static_cast<size_t>(kGateSlots), "host transport: a gated sum has at most 8 operands (the own one and 7 incoming)");
+    P2P_CHECK(gate && gate_rows(bytes, row_elems) > 0, "host transport: a gated sum is whole rows of row_elems bf16 under a gate table");
+    reduce_from(dst, bytes, local_src, peers, src_offset, ReduceType::Bf16);
+    reduce_.gate = gate;
+    reduce_.row_elems = row_elems;
+  }
+
   // ---- wire formats: the packed image travels, the CPU widens it ----
   bool supports_wire() const override { return true; }
   void fill_packed(void* p, size_t payload_bytes, uint64_t seed, WireFormat fmt) override {
@@ -505,7 +573,10 @@ class HostTransport final : public Transport {
     if (reduce_.dst && !discarding()) {
       std::vector<const void*> operands{reduce_.local_src};
       for (size_t i = 0; i < reduce_.npeers; ++i) operands.push_back(scratch_.data() + i * reduce_.bytes);
-      host_reduce(reduce_.dst, operands.data(), static_cast<int>(operands.size()), reduce_.bytes, reduce_.dtype);
+      if (reduce_.gate)
+        host_gated_reduce(reduce_.dst, operands.data(), static_cast<int>(operands.size()), reduce_.bytes, reduce_.gate, reduce_.row_elems);
+      else
+        host_reduce(reduce_.dst, operands.data(), static_cast<int>(operands.size()), reduce_.bytes, reduce_.dtype);
     }
     reduce_ = {};
     if (wire_reduce_.dst && !discarding()) {
@@ -540,6 +611,8 @@ class HostTransport final : public Transport {
     const void* local_src = nullptr;
     ReduceType dtype = ReduceType::Off;
     size_t npeers = 0;
+    const void* gate = nullptr;  // reduce_gated_from: the gate table, rows of row_elems bf16
+    size_t row_elems = 0;
   };
   struct PendingWireReduce {
     void* dst = nullptr;

@@ -290,6 +290,20 @@ class IpcTransport final : public GpuTransport {
     }
   }
 
+  // ---- gated receive-and-reduce (transport.hpp): the same op, launched as the
+  // gated reduce kernel (kernels.hpp launch_gated_reduce), still one launch.
+  bool supports_reduce_gate() const override { return engine_ == "kernel"; }
+  void reduce_gated_from(void* dst, size_t bytes, const void* local_src, const std::vector<int>& peers, size_t src_offset,
+                         const void* gate, size_t row_elems) override {
+    P2P_CHECK(supports_reduce_gate(), "ipc transport: --reduce-gate needs --ipc-engine kernel");
+    P2P_CHECK(peers.size() < static_cast<size_t>(dev::kMaxReduceSrcs),
+              "ipc transport: a gated sum has at most 8 operands (the own one and 7 incoming)");
+    P2P_CHECK(gate && gate_rows(bytes, row_elems) > 0, "ipc transport: a gated sum is whole rows of row_elems bf16 under a gate table");
+    reduce_from(dst, bytes, local_src, peers, src_offset, ReduceType::Bf16);
+    reduce_.gate = gate;  // under an injected skip fault dst stays unset and nothing is launched
+    reduce_.row_elems = row_elems;
+  }
+
   // ---- wire formats (transport.hpp): the pull engine's unpack kernel reads
   // the peers' MXFP8 / MXFP4 images and stores bf16, one launch per group.
   bool supports_wire() const override { return engine_ == "kernel"; }
@@ -495,6 +509,19 @@ class IpcTransport final : public GpuTransport {
     // Kernel engine: the checked kernel when the group has checked receives
     // (the runner posts a group either all checked or all plain; plain ones
     // next to them go in the plain kernel), the plain kernel otherwise.
+    if (reduce_.dst && reduce_.gate) {
+      dev::GatedReduceOp op;
+      op.dst = reduce_.dst;
+      op.bytes = reduce_.bytes;
+      op.gate = reduce_.gate;
+      op.row_elems = reduce_.row_elems;
+      for (size_t k = 0; k < reduce_.srcs.size(); ++k) {
+        if (reduce_.coherent[k]) op.coherent_mask |= 1u << op.nsrc;
+        op.src[op.nsrc++] = reduce_.srcs[k];
+      }
+      dev::launch_gated_reduce(&op, 1, stream_);
+      reduce_ = {};
+    }
     if (reduce_.dst) {
       // A bf16 fan-in above 8 (more than 8 ranks) carries f32 partial sums in scratch.
       const size_t need = reduce_.dtype == ReduceType::Bf16 && reduce_.srcs.size() > static_cast<size_t>(dev::kMaxReduceSrcs)
@@ -684,6 +711,8 @@ class IpcTransport final : public GpuTransport {
     ReduceType dtype = ReduceType::Off;
     std::vector<const void*> srcs;   // operand 0: the own shard
     std::vector<unsigned char> coherent;  // per source: a peer's mapped buffer
+    const void* gate = nullptr;  // reduce_gated_from: the gate table and its row length
+    size_t row_elems = 0;
   } reduce_;
   // Pull kernel: the open group's recv_unpacked ops, launched in flush().
   std::vector<dev::UnpackOp> unpack_ops_;

@@ -260,6 +260,56 @@ def reference_reduce(operands, dtype: str) -> torch.Tensor:
     return lo16 | (hi16 << 16)
 
 
+def gated_reduce_(dst: torch.Tensor, srcs, gates: torch.Tensor, row_elems: int, *, coherent: bool = False,
+                  max_blocks: int = 0, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """The expert combine with the gfx950 gated reduce kernel (stream-ordered;
+    ``--reduce-gate``): the tensors' bytes are rows of ``row_elems`` bf16 (a
+    multiple of 512), and row r of ``dst`` = the sum over the 1..8 ``srcs`` k, in
+    that order, of gate k of entry r of ``gates`` times row r of source k, in
+    float32, rounded once.  ``gates``: 16 bytes (8 bf16) per row, local memory
+    (csrc/reduce_gate_op.hpp)."""
+    nbytes = _check_tensor(dst)
+    if any(_check_tensor(s) != nbytes for s in srcs):
+        raise ValueError("gated_reduce_: dst and every source have one size")
+    if row_elems <= 0 or nbytes % (2 * row_elems) or _check_tensor(gates) < nbytes // (2 * row_elems) * 16:
+        raise ValueError("gated_reduce_: whole rows of row_elems bf16 and 16 bytes of gates per row")
+    require_native().gated_reduce(dst.data_ptr(), [s.data_ptr() for s in srcs], nbytes, gates.data_ptr(), row_elems,
+                                  _stream(stream), coherent, max_blocks)
+    return dst
+
+
+def reference_gates(rows: int, seed: int, device="cpu") -> torch.Tensor:
+    """The gate table of ``rows`` entries from stream ``seed`` as int64 words, 4
+    per row (gate k of a row: half ``k & 1`` of its word ``k // 2``): each
+    half-word h of the PRNG word becomes the positive bf16
+    ``((123 + ((h >> 7) & 3)) << 7) | (h & 0x7F)``, a value in [2**-4, 1)."""
+    w = reference_words(0, 4 * rows, seed, device)
+    halves = [(((123 + ((h >> 7) & 3)) << 7) | (h & 0x7F)) for h in (w & 0xFFFF, w >> 16)]
+    return halves[0] | (halves[1] << 16)
+
+
+def reference_gated_reduce(operands, gates: torch.Tensor, row_elems: int) -> torch.Tensor:
+    """What :func:`gated_reduce_` leaves, as int64 words: ``operands`` are int64
+    bf16 word tensors (:func:`reference_operands`), ``gates`` the table's words
+    (:func:`reference_gates`).  Plain PyTorch on the CPU: every bf16 widened to
+    ``torch.float32``, gate k's multiply, sequential float32 adds in operand
+    order, one ``.to(torch.bfloat16)``."""
+    assert 1 <= len(operands) <= 8 and row_elems % 512 == 0
+    row_words = row_elems // 2
+    table = gates.cpu().reshape(-1, 4)
+    lo = hi = None
+    for k, o in enumerate(o.cpu() for o in operands):
+        g16 = (table[:, k // 2] >> (16 * (k & 1))) & 0xFFFF
+        g = _words_to_f32(g16 << 16).repeat_interleave(row_words)
+        p_lo = g * _words_to_f32((o << 16) & M32)
+        p_hi = g * _words_to_f32(o & 0xFFFF0000)
+        lo = p_lo if lo is None else lo + p_lo
+        hi = p_hi if hi is None else hi + p_hi
+    lo16 = lo.to(torch.bfloat16).view(torch.int16).to(torch.int64) & 0xFFFF
+    hi16 = hi.to(torch.bfloat16).view(torch.int16).to(torch.int64) & 0xFFFF
+    return lo16 | (hi16 << 16)
+
+
 def words_to_bytes(w: torch.Tensor) -> torch.Tensor:
     """int64 words in [0, 2**32) as a uint8 tensor (little-endian)."""
     return torch.stack([(w >> (8 * k)) & 0xFF for k in range(4)], dim=1).to(torch.uint8).reshape(-1)
